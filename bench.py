@@ -1,6 +1,7 @@
 """Headline benchmark: consensus updates/sec (N oracles x D dims, batched) at 1/2/4/8 MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5|c4|c1] [--batch B]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 Configs (BASELINE.json):
@@ -11,10 +12,15 @@ Configs (BASELINE.json):
       health metrics (reliability sum, OK count) are folded on the device every step and all-reduced
       over RCCL once per graph replay (``graph_steps`` steps, reported on the line).  Storage: fp32 -- the
       reference computes on the 1e-6 wsad grid (contract/src/signed_decimal.cairo:82-83) and fp32 holds
-      every grid value of [0, 1] exactly; the bf16-storage step is measured too and reported as the
-      extra field ``config.alt_storage``.
-  c2: 64 oracles x 1024 dims, 10k instances per GPU (bf16, as BASELINE.json names it; fp32 storage
-      reported as ``config.alt_storage``), one full consensus round per instance per step.
+      every grid value of [0, 1] exactly; with ``--full`` the bf16-storage step is measured too and
+      reported as the extra field ``config.alt_storage``.
+  c2: 64 oracles x 1024 dims, 10k instances per GPU (bf16, as BASELINE.json names it; with ``--full``
+      fp32 storage is reported as ``config.alt_storage``), one full consensus round per instance per step.
+A plain run sets up, warms up, times exactly ``--steps`` steps and prints the result line.  ``--full`` adds
+the side measurements, each a timed run of its own after the headline: ``config.alt_storage`` (c2, c3),
+``config.exact_stream`` (c3), ``config.alt_precision`` and ``config.cls_pool`` (c4).  ``--dump-outputs DIR``
+writes the round outputs the headline engine holds after its last timed step as ``DIR/<name>.npy``
+(inputs are seeded: the same arguments give the same arrays).
 Weak scaling: per-GPU instances are fixed; ``value`` is the whole-job consensus rounds per second.
 Synthetic data (Beta(20,20) honest oracles, U(0,1) failing), random state.
 """
@@ -96,6 +102,35 @@ def _dtype_name(mode: str, storage: str, c: dict) -> str:
     if mode == "exact":
         return f"{storage}-wsad"
     return {"fp32": "fp32", "bf16": "bf16"}.get(storage, c.get("dtype", "bf16"))
+
+
+DUMP_BUDGET = 56 * 1000 * 1000   # bytes of --dump-outputs arrays, all ranks together
+
+
+def dump_outputs(path: str, eng, rank: int = 0, world: int = 1) -> None:
+    """Write the round outputs a caller reads from the engine (the contract's getters, per-instance status and
+    reliable flags) as ``path/<name>.npy`` (rank r > 0: ``<name>.rank<r>.npy``): float32, float64 for the exact
+    engine's wsad integers.  Above the size budget a fixed seeded sample of the instances is written, their
+    indices as ``instances.npy``."""
+    import numpy as np
+    eng.pipeline_join()
+    wide = torch.float64 if eng.mode == "exact" else torch.float32
+    arrays = {"consensus": eng.get_consensus_value(), "skewness": eng.get_skewness(),
+              "kurtosis": eng.get_kurtosis(), "reliability": eng.get_reliability(), "status": eng.status,
+              "reliable": eng.reliable, "consensus_active": eng.consensus_active}
+    per_inst = sum(a[0].numel() for a in arrays.values()) * (8 if wide == torch.float64 else 4)
+    keep = max(1, (DUMP_BUDGET // max(1, world)) // max(1, per_inst))
+    sel = None
+    if keep < eng.B:
+        sel = np.sort(np.random.default_rng(0).choice(eng.B, size=keep, replace=False))
+        arrays["instances"] = torch.from_numpy(sel)
+        sel = torch.from_numpy(sel).to(eng.device)
+    os.makedirs(path, exist_ok=True)
+    suffix = f".rank{rank}" if rank else ""
+    for name, a in arrays.items():
+        if sel is not None and name != "instances":
+            a = a.index_select(0, sel)
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a.to(wide).cpu().numpy())
 
 
 _MARK_SEQ = 0   # timed regions bracketed by marker kernels so far (--markers)
@@ -403,6 +438,12 @@ def main():
     ap.add_argument("--log", default=None, help="append the result record to this JSON-lines file")
     ap.add_argument("--markers", action="store_true",
                     help="profiling: bracket each timed region with marker kernels (tools/replay_kernels.py)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the headline engine's round outputs (consensus, skewness, "
+                         "kurtosis, reliability, status, reliable flags) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements after the headline, each a timed run of its own: "
+                         "alt_storage (c2, c3), exact_stream (c3), alt_precision and cls_pool (c4)")
     ap.add_argument("--kernel-table", type=int, default=0, help="profile N extra steps (torch.profiler) "
                     "after the timed region and add the per-kernel table to the log record")
     args = ap.parse_args()
@@ -440,7 +481,7 @@ def main():
     from svoc.utils.metrics import algorithmic_bytes_per_round
     fast = (args.mode or c.get("mode", "fast")) == "fast"
     storage = args.storage or (c.get("storage") if fast else None)
-    alt = c.get("alt_storage") if (fast and args.storage is None and dev.type == "cuda") else None
+    alt = c.get("alt_storage") if (args.full and fast and args.storage is None and dev.type == "cuda") else None
     scale = 1 if dshard else world   # D-sharding: all ranks share the same B instances
 
     def min_gbps(res, storage_bytes):
@@ -467,6 +508,8 @@ def main():
     }
     if args.config in ("c2", "c3") and mode == "fast":
         out["config"]["hbm_gbps_min_traffic"] = min_gbps(r, eng.values.element_size())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, rank, world)
     log_eng, log_step = eng, r["step"]
     if alt:
         # the same step at the alternative storage dtype (a fresh engine; the first one is freed first)
@@ -481,7 +524,7 @@ def main():
             "hbm_gbps_min_traffic": min_gbps(ra, ra["eng"].values.element_size()),
             "rank_ms_spread": [min(ra["rank_ms"]), max(ra["rank_ms"])]}
         log_eng, log_step = ra["eng"], ra["step"]
-    if args.config == "c3" and fast and args.storage is None and dev.type == "cuda" and not dshard:
+    if args.full and args.config == "c3" and fast and args.storage is None and dev.type == "cuda" and not dshard:
         # the transaction-faithful form of the same stream: the EXACT engine (wsad, bit-identical to the
         # contract), every one of the 64 updates per instance its own transaction (store + full round +
         # revert on failure: contract.cairo:588-603).  Fixed 2 timed steps (1 warm-up): ~0.45 s each.
@@ -500,7 +543,7 @@ def main():
             "unit": "consensus rounds/s (one per update transaction)", "steps": ax.steps, "warmup": ax.warmup,
             "ms_per_step": 1e3 * rx["elapsed"] / ax.steps, "ok_fraction": rx["ok"]}
         log_eng, log_step = rx["eng"], rx["step"]
-    if c.get("alt_precision") == "fp32" and dev.type == "cuda":
+    if args.full and c.get("alt_precision") == "fp32" and dev.type == "cuda":
         # c4 at the reference's precision: the same step with fp32 encoder weights / activations
         r = eng = None
         log_eng = log_step = None
@@ -515,7 +558,7 @@ def main():
                        else "fp32 GEMMs (hipBLASLt)"),
             "fp32_gemm": _enc_fp32_gemm()}
         log_eng, log_step = rp["eng"], rp["step"]
-    if args.config == "c4" and dev.type == "cuda":
+    if args.full and args.config == "c4" and dev.type == "cuda":
         # the reference's head (client/oracle_scheduler.py:23-40: the <s> state through the classification
         # head, SamLowe/roberta-base-go_emotions) -- same encoder, <s> pooling instead of the masked mean
         r = eng = None

@@ -155,6 +155,59 @@ def test_bench_fp32_storage_cpu(tmp_path):
     assert out["value"] > 0 and out["config"]["ok_fraction"] == 1.0
 
 
+def test_bench_dump_outputs_repeatable_cpu(tmp_path):
+    """bench.py --dump-outputs DIR: the round outputs after the last timed step as float32 .npy files, the same
+    arrays from run to run (seeded inputs); --full is accepted and leaves the headline arrays unchanged."""
+    import numpy as np
+    cfg = _cpu_cfg(tmp_path)
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config-file", cfg, "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(d)] + extra, capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+        dumps.append({p.name: np.load(p) for p in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert {"consensus.npy", "skewness.npy", "kurtosis.npy", "reliability.npy", "status.npy"} <= set(a)
+    assert set(a) == set(b)
+    assert a["consensus.npy"].shape == (8, 64) and a["reliability.npy"].shape == (8, 2)
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        assert np.array_equal(a[k], b[k]), k
+    assert (a["status.npy"] == 0).all() and 0.0 < a["consensus.npy"].min() <= a["consensus.npy"].max() < 1.0
+
+
+def test_bench_dump_outputs_samples_within_budget(tmp_path, monkeypatch):
+    """Above the size budget dump_outputs writes a fixed seeded sample of the instances (the same rows of
+    every array, their indices in instances.npy); the exact engine's wsad integers go out as float64."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    e = ConsensusEngine(ConsensusConfig(n_oracles=7, dimension=3, n_failing_oracles=2), 16, device="cpu", mode="exact")
+    e.randomize(seed=2)
+    e.run_round()
+    per_inst = (3 * 3 + 2 + 1 + 7 + 1) * 8
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 5 * per_inst + 1)
+    picks = []
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), e)
+        got = {p.name: np.load(p) for p in sorted((tmp_path / name).glob("*.npy"))}
+        assert sum(v.nbytes for k, v in got.items() if k != "instances.npy") <= bench.DUMP_BUDGET
+        idx = got["instances.npy"].astype(np.int64)
+        assert len(idx) == 5 and (np.diff(idx) > 0).all() and 0 <= idx[0] and idx[-1] < 16
+        assert all(v.dtype == np.float64 for v in got.values())
+        assert np.array_equal(got["consensus.npy"], e.consensus[idx].double().numpy())
+        assert np.array_equal(got["reliability.npy"], e.rel[idx].double().numpy())
+        assert np.array_equal(got["status.npy"], e.status[idx].double().numpy())
+        picks.append(idx)
+    assert np.array_equal(picks[0], picks[1])
+
+
 def test_bench_exact_transactional_stream_cpu(tmp_path):
     """configs/c*_exact_stream.yaml's form: exact mode, every update its own transaction -- rounds/s
     counts one round per update (U per instance per step)."""

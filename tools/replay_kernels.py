@@ -3,11 +3,11 @@ that run between the two `svoc_bench_marker_kernel` launches of one timed region
 setup (stream-pool RNG, warm-up, graph capture) never appears.  Per kernel: calls, total / average µs, and the
 share of the timed window; per step: µs of each kernel per step and the window per step.
 
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/rk_c3 -o run -- python3 bench.py --config c3 --markers
-    python tools/replay_kernels.py gpurun_out/rk_c3 "title" [region=1] [steps=20] > profiles/r6_c3_replay_kernels.md
+    rocprofv3 --kernel-trace --output-format csv -d out/rk_c3 -o run -- python3 bench.py --config c3 --full --markers
+    python tools/replay_kernels.py out/rk_c3 "title" [region=1] [steps=20] > profiles/r6_c3_replay_kernels.md
 
-Region k is the k-th timed region of the run (bench.py measures the headline first, then alt_storage /
-exact_stream / alt_precision / cls_pool in that order, each with its own markers).
+Region k is the k-th timed region of the run (bench.py measures the headline first, then with --full
+alt_storage / exact_stream / alt_precision / cls_pool in that order, each with its own markers).
 """
 from __future__ import annotations
 
