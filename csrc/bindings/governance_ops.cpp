@@ -1,12 +1,14 @@
-// torch.ops.svoc.governance: batched update_proposition / vote_for_a_proposition.
+// torch.ops.svoc.governance: batched update_proposition / vote_for_a_proposition; find_address: batched lookup.
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include "svoc/address_lookup.hpp"
 #include "svoc/governance.hpp"
 #include "svoc/ops.hpp"
 
 extern "C" int svoc_governance(const svoc::GovState* g, const svoc::GovAction* a, hipStream_t s);
+extern "C" int svoc_find_address(const svoc::AddrLookup* p, hipStream_t s);
 
 namespace svoc {
 namespace {
@@ -93,6 +95,48 @@ void governance_seq_hip(const at::Tensor& admins, at::Tensor oracle_addr, at::Te
   TORCH_CHECK(rc == 0, "svoc_governance failed: ", rc);
 }
 
+// find_address: batched find_oracle_index / admin lookup (address_lookup.hpp).  Writes `out` in place: no
+// allocation and no host synchronisation, so a captured graph replays it.
+AddrLookup prep_lookup(const at::Tensor& table, const at::Tensor& inst, const at::Tensor& addr, at::Tensor& out) {
+  auto chk = [&](const at::Tensor& t, const char* n) {
+    TORCH_CHECK(t.device() == table.device(), "find_address: ", n, " must be on ", table.device(), " (got ",
+                t.device(), ")");
+    TORCH_CHECK(t.scalar_type() == at::kLong && t.is_contiguous(), "find_address: ", n, ": contiguous int64");
+  };
+  chk(table, "table"); chk(inst, "inst"); chk(addr, "addr"); chk(out, "out");
+  TORCH_CHECK(table.dim() == 3 && table.size(2) == 4, "find_address: table: [B, M, 4]");
+  TORCH_CHECK(table.size(1) < (int64_t(1) << 30), "find_address: table too wide");
+  const int64_t K = inst.numel();
+  TORCH_CHECK(inst.dim() == 1 && addr.dim() == 2 && addr.size(0) == K && addr.size(1) == 4 && out.dim() == 1 &&
+              out.numel() == K, "find_address: inst [K], addr [K, 4], out [K]");
+  AddrLookup p{};
+  p.B = table.size(0); p.M = (int)table.size(1); p.K = K;
+  if (K == 0) return p;
+  p.table = table.data_ptr<int64_t>(); p.inst = inst.data_ptr<int64_t>(); p.addr = addr.data_ptr<int64_t>();
+  p.out = out.data_ptr<int64_t>();
+  return p;
+}
+
+void find_address_cpu(const at::Tensor& table, const at::Tensor& inst, const at::Tensor& addr, at::Tensor out) {
+  TORCH_CHECK(table.device().is_cpu(), "find_address: table must be a host tensor here");
+  const AddrLookup p = prep_lookup(table, inst, addr, out);
+  for (int64_t k = 0; k < p.K; ++k) p.out[k] = find_address_one(p, k);
+}
+
+void find_address_hip(const at::Tensor& table, const at::Tensor& inst, const at::Tensor& addr, at::Tensor out) {
+  // (the dispatcher comes here when ANY argument is a device tensor: a host tensor among them is refused by
+  // prep_lookup before a kernel could read through its pointer)
+  TORCH_CHECK(table.device().is_cuda(), "find_address: table must be on the device of the other tensors (got ",
+              table.device(), ")");
+  const AddrLookup p = prep_lookup(table, inst, addr, out);
+  if (p.K == 0) return;
+  // the kernel reads addresses as 16-B vectors
+  TORCH_CHECK((((uintptr_t)p.table | (uintptr_t)p.addr) & 15) == 0, "find_address: table / addr not 16-B aligned");
+  auto stream = c10::hip::getCurrentHIPStream(table.device().index()).stream();
+  const int rc = svoc_find_address(&p, stream);
+  TORCH_CHECK(rc == 0, "svoc_find_address failed: ", rc);
+}
+
 }  // namespace
 
 void register_governance_defs(torch::Library& m) {
@@ -105,14 +149,17 @@ void register_governance_defs(torch::Library& m) {
       "Tensor(d!) prop_idx, Tensor(e!) prop_addr, Tensor inst, Tensor caller, Tensor kind, Tensor arg0, "
       "Tensor arg1, Tensor addr, bool enable, int majority, Tensor order, Tensor(f!) status, "
       "Tensor(g!) applied) -> ()");
+  m.def("find_address(Tensor table, Tensor inst, Tensor addr, Tensor(a!) out) -> ()");
 }
 void register_governance_cpu(torch::Library& m) {
   m.impl("governance", &governance_cpu);
   m.impl("governance_seq", &governance_seq_cpu);
+  m.impl("find_address", &find_address_cpu);
 }
 void register_governance_hip(torch::Library& m) {
   m.impl("governance", &governance_hip);
   m.impl("governance_seq", &governance_seq_hip);
+  m.impl("find_address", &find_address_hip);
 }
 
 }  // namespace svoc

@@ -12,7 +12,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from .codec import as_wsad, felt_to_i128, i128_to_felt, wsad_tensor_to_felts
+from .codec import addresses_to_limbs, as_wsad, felt_to_i128, i128_to_felt, wsad_tensor_to_felts
 from .config import WSAD, ConsensusConfig
 from .engine import ConsensusEngine
 from .governance import Governance
@@ -35,7 +35,7 @@ class ConsensusService:
     def update_predictions(self, items: Sequence[Tuple[int, int, Sequence]]) -> List[Status]:
         """items: (instance, caller_address, prediction).  Predictions are wsad ints (exact mode)
         or floats (fast mode).  Returns one status per item (reverts do not raise)."""
-        inst, orc, vals, pre = [], [], [], []
+        pre, cand = [], []
         for k, (b, caller, pred) in enumerate(items):
             if len(pred) != self.cfg.dimension:
                 raise ValueError("prediction length != dimension")
@@ -44,11 +44,19 @@ class ConsensusService:
                 if any(not (0 <= x <= hi) for x in pred):
                     pre.append((k, Status.INTERVAL_INPUT))
                     continue
-            o = self.gov.oracle_index(int(b), caller) if 0 <= int(b) < self.B else None
-            if o is None:
+            if not (0 <= int(b) < self.B and 0 <= int(caller) < (1 << 256)):
+                pre.append((k, Status.NOT_ORACLE))       # no such instance / no stored address can match
+                continue
+            cand.append((k, int(b), int(caller), pred))
+        # every caller of the call in one device lookup (find_oracle_index, contract.cairo:505-518)
+        found = (self.gov.resolve_oracles([c[1] for c in cand], addresses_to_limbs(c[2] for c in cand))
+                 .cpu().tolist() if cand else [])
+        inst, orc, vals = [], [], []
+        for (k, b, _, pred), o in zip(cand, found):
+            if o < 0:
                 pre.append((k, Status.NOT_ORACLE))       # 'not an oracle' (contract.cairo:596)
                 continue
-            inst.append(int(b)); orc.append(o); vals.append(list(pred))
+            inst.append(b); orc.append(o); vals.append(list(pred))
         out: List[Status] = [Status.OK] * len(items)
         for k, st in pre:
             out[k] = st
@@ -60,6 +68,19 @@ class ConsensusService:
                 if all(k != p for p, _ in pre):
                     out[k] = Status(next(it))
         return out
+
+    def update_batch(self, inst, caller, values, updates_per_instance: Optional[int] = None) -> torch.Tensor:
+        """Authenticated tensor form of ``update_prediction``: inst [K] int64, caller [K, 4] int64 address limbs
+        (:func:`svoc.codec.addresses_to_limbs`), values [K, D] (int64 wsad in exact mode, floats in fast mode)
+        -> one :class:`Status` code per update, [K] int32 on the device.
+
+        One lookup launch resolves every caller against the device address table
+        (:meth:`Governance.resolve_oracles`); (inst, oracle index, values) then go to :meth:`ConsensusEngine.step`
+        unchanged.  An unknown caller or instance resolves to -1, which the update kernels report as NOT_ORACLE
+        after the interval / finite checks -- the contract's order (contract.cairo:588-596).  No per-item host
+        work and no device->host copy beyond what ``step`` itself does."""
+        inst = torch.as_tensor(inst, dtype=torch.int64, device=self.engine.device).reshape(-1)
+        return self.engine.step(inst, self.gov.resolve_oracles(inst, caller), values, updates_per_instance)
 
     def governance(self, actions) -> Tuple[List[Status], List[bool]]:
         """update_proposition / vote_for_a_proposition transactions (contract.cairo:661-738).  ``actions``: a list

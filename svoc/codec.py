@@ -120,6 +120,12 @@ def limbs_to_address(limbs: Sequence[int]) -> int:
     return sum((int(l) & 0xFFFFFFFFFFFFFFFF) << (64 * i) for i, l in enumerate(limbs))
 
 
+def addresses_to_limbs(addrs: Iterable[int], device=None) -> torch.Tensor:
+    """Address ints -> [K, 4] int64 limb tensor (the ``caller`` / ``addr`` argument of the batched paths)."""
+    rows = [address_to_limbs(int(a)) for a in addrs]
+    return torch.tensor(rows, dtype=torch.int64, device=device).reshape(len(rows), 4)
+
+
 def shortstring(s: str) -> int:
     """Cairo short string literal ('Akashi') -> felt (big-endian ASCII)."""
     return int.from_bytes(s.encode("ascii"), "big")

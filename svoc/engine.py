@@ -101,8 +101,11 @@ class _PendingBatches:
             self.rows = torch.zeros(e.B, e.N, dtype=torch.bool, device=e.device)
         for inst, oracle, *_ in entries:
             ok = (inst >= 0) & (inst < e.B) & (oracle >= 0) & (oracle < e.N)
-            ic, oc = inst.clamp(0, e.B - 1), oracle.clamp(0, e.N - 1)
-            self.rows[ic, oc] = self.rows[ic, oc] | ok
+            # only valid ids mark a cell: counted per cell (no host sync), so an invalid entry that clamps
+            # onto a valid entry's cell (oracle -1 -> 0: an unauthenticated caller) cannot erase its mark
+            cell = inst.clamp(0, e.B - 1) * e.N + oracle.clamp(0, e.N - 1)
+            hits = torch.zeros(e.B * e.N, dtype=torch.int32, device=e.device).index_add_(0, cell, ok.to(torch.int32))
+            self.rows |= hits.view(e.B, e.N) > 0
 
     def restore(self, status: torch.Tensor, active: torch.Tensor) -> None:
         """Roll back the pending batches of the instances whose round ran (``active``) and reverted."""

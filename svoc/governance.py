@@ -15,13 +15,13 @@ WRONG_ADMIN_INDEX instead of writing an unchecked storage key (§2.8-8).
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import ops as svops
-from .codec import address_to_limbs, limbs_to_address
+from .codec import address_to_limbs, addresses_to_limbs, limbs_to_address
 from .status import ConsensusRevert, Status
 
 PROPOSE, VOTE = 0, 1
@@ -43,7 +43,6 @@ class Governance:
         self.prop_idx = torch.zeros(B, n_admins, dtype=torch.int32, device=d)
         self.prop_addr = torch.zeros(B, n_admins, 4, dtype=torch.int64, device=d)
         self._ops = svops.ops()
-        self._oracle_cache: Optional[List[Dict[int, int]]] = None
         self.replacements = 0
 
     # ------------------------------------------------------------------ addresses
@@ -59,20 +58,41 @@ class Governance:
         if self.A:
             self.admins.copy_(pack(list(admins), self.A))
         self.oracle_addr.copy_(pack(list(oracles), self.N))
-        self._oracle_cache = None
+
+    def _resolve(self, table: torch.Tensor, inst, caller, out: Optional[torch.Tensor]) -> torch.Tensor:
+        d = self.device
+        inst = torch.as_tensor(inst, dtype=torch.int64, device=d).reshape(-1).contiguous()
+        K = inst.numel()
+        caller = torch.as_tensor(caller, dtype=torch.int64, device=d).reshape(K, 4).contiguous()
+        if out is None:
+            out = torch.empty(K, dtype=torch.int64, device=d)
+        self._ops.find_address(table, inst, caller, out)
+        return out
+
+    def resolve_oracles(self, inst, caller, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Batched find_oracle_index (contract.cairo:505-518): inst [K] int64, caller [K, 4] int64 limbs ->
+        [K] int64, the lowest oracle index whose address equals the caller's in that instance, -1 for an
+        unknown caller or an instance outside [0, B).  One launch over the device table (the only copy of
+        the addresses: a replacement or a direct write to ``oracle_addr`` is seen by the next call), no host
+        synchronisation; with device inputs and ``out`` given, no allocation either (graph-capturable)."""
+        return self._resolve(self.oracle_addr, inst, caller, out)
+
+    def resolve_admins(self, inst, caller, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """:meth:`resolve_oracles` over the admin table."""
+        return self._resolve(self.admins, inst, caller, out)
+
+    def _index_of(self, resolve, b: int, addr: int) -> Optional[int]:
+        if not (0 <= int(b) < self.B and 0 <= int(addr) < (1 << 256)):
+            return None          # no such instance / no stored address is outside the limb range
+        i = int(resolve([int(b)], addresses_to_limbs([addr]))[0])
+        return i if i >= 0 else None
 
     def oracle_index(self, b: int, addr: int) -> Optional[int]:
-        """find_oracle_index (contract.cairo:505-518) with a host-side hash map cache."""
-        if self._oracle_cache is None:
-            host = self.oracle_addr.cpu().tolist()
-            self._oracle_cache = [{limbs_to_address(l): i for i, l in reversed(list(enumerate(r)))} for r in host]
-        return self._oracle_cache[b].get(int(addr))
+        """find_oracle_index (contract.cairo:505-518) for one caller."""
+        return self._index_of(self.resolve_oracles, b, addr)
 
     def admin_index(self, b: int, addr: int) -> Optional[int]:
-        for i, l in enumerate(self.admins[b].cpu().tolist()):
-            if limbs_to_address(l) == int(addr):
-                return i
-        return None
+        return self._index_of(self.resolve_admins, b, addr)
 
     def oracle_list(self, b: int) -> List[int]:
         return [limbs_to_address(l) for l in self.oracle_addr[b].cpu().tolist()]
@@ -135,7 +155,6 @@ class Governance:
         self._ops.governance_seq(self.admins, self.oracle_addr, self.votes, self.prop_tag, self.prop_idx,
                                  self.prop_addr, inst, caller, kind, arg0, arg1, addr, self.enable, self.majority,
                                  order, status, applied)
-        self._oracle_cache = None
         return status, applied
 
     def submit_tensors(self, inst, caller, kind, arg0, arg1, addr):
@@ -145,7 +164,6 @@ class Governance:
         ap = torch.zeros(K, dtype=torch.uint8, device=self.device)
         self._ops.governance(self.admins, self.oracle_addr, self.votes, self.prop_tag, self.prop_idx,
                              self.prop_addr, inst, caller, kind, arg0, arg1, addr, self.enable, self.majority, st, ap)
-        self._oracle_cache = None
         return st, ap
 
     # ------------------------------------------------------------------ getters

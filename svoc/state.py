@@ -92,7 +92,6 @@ def load(path: str, device="cpu"):
     if cfg.n_admins:
         g.admins.copy_(t["admins"].to(dev))
     g.oracle_addr.copy_(t["oracle_address"].to(dev))
-    g._oracle_cache = None
     e.values[:, :, : e.D].copy_(t["oracles_values"].to(dev, e.vdtype))
     e.enabled.copy_(t["enabled"].to(dev))
     e.reliable.copy_(t["reliable"].to(dev))
