@@ -349,24 +349,76 @@ void exact_round_cpu(const at::Tensor& values, const c10::optional<at::Tensor>& 
   exact_round_batch_cpu(eb, cpu_threads());
 }
 
+// the column kernel's environment switches (tests, A/B)
+bool exact_force_i128() {
+  const char* force = std::getenv("SVOC_EXACT_I128");
+  return force && force[0] == '1';
+}
+void column_kernel_switches(ExactParams& p) {
+  const char* only = std::getenv("SVOC_EXACT_WSAD_ONLY");
+  p.skip_fallback = only && only[0] == '1';
+  const char* md = std::getenv("SVOC_EXACT_WSAD_MIN_D");   // tests: route small instances through it too
+  p.wsad_min_d = md ? std::atoi(md) : 64;
+}
+
+// What exact_round and exact_verdict share on the GPU: the round's inputs and switches in an ExactParams, the i128
+// kernel's workspace, and the column kernel's buffers (the caller sets the output pointers).
+struct ExactLaunch {
+  ExactParams p{};
+  at::Tensor work, stage, fallback;
+
+  ExactLaunch(const at::Tensor& values, const c10::optional<at::Tensor>& active, int64_t n_failing, bool constrained,
+              int64_t max_spread, bool legacy, int64_t mode, int64_t rel_dim, const c10::optional<at::Tensor>& stats) {
+    p.legacy = legacy ? 1 : 0;
+    p.mode = (int)mode;
+    p.rel_dim = (int)rel_dim;
+    p.values = values.data_ptr();
+    p.val32 = values.scalar_type() == at::kInt ? 1 : 0;
+    p.B = (int)values.size(0); p.N = (int)values.size(1); p.D = (int)values.size(2);
+    TORCH_CHECK(p.N >= 1 && p.N <= kExactMaxN, "GPU exact path supports N <= ", kExactMaxN);
+    p.active = active_ptr(active, p.B, values.device());
+    p.n_failing = (int)n_failing;
+    p.constrained = constrained ? 1 : 0;
+    p.max_spread = max_spread;
+    if (stats.has_value() && stats->defined()) {
+      // [0] += rounds the wide-column unconstrained kernel committed, [1] += rounds left to the i128 kernel
+      TORCH_CHECK(stats->scalar_type() == at::kInt && stats->numel() >= 2 && stats->device() == values.device(),
+                  "stats: int32 [>= 2] on the values' device");
+      p.xstats = (unsigned int*)stats->data_ptr();
+    }
+    if ((int64_t)p.D * kExactWsCols * 8 > 64 * 1024) {  // wide instances: per-column intermediates in HBM
+      work = at::empty({(int64_t)p.B, kExactWsCols, (int64_t)p.D}, values.options().dtype(at::kLong));
+      p.work = work.data_ptr<int64_t>();
+    }
+  }
+
+  // column-parallel kernel (consensus_wsad.hip), the i128 kernel for the instances it flags;
+  // SVOC_EXACT_I128=1 forces the i128 kernel everywhere (tests, A/B)
+  bool column_kernel(const at::Tensor& values) {
+    if (p.N < 4 || exact_force_i128()) return false;
+    fallback = at::empty({(int64_t)p.B}, values.options().dtype(at::kByte));
+    p.fallback = fallback.data_ptr<uint8_t>();
+    column_kernel_switches(p);
+    return true;
+  }
+  // the full column kernel's stage: c1, consensus, skewness, kurtosis; the window keys; unconstrained: the
+  // columns' base words
+  void alloc_stage(const at::Tensor& values) {
+    p.win_h = p.mode == 0 && p.constrained && !p.legacy ? exact_win_h(p.N, p.n_failing) : 0;
+    stage = at::empty({(int64_t)p.B, 4 + 2 * p.win_h + (p.constrained ? 0 : 2), (int64_t)p.D},
+                      values.options().dtype(at::kInt));
+    p.stage = stage.data_ptr<int32_t>();
+  }
+};
+
 void exact_round_hip(const at::Tensor& values, const c10::optional<at::Tensor>& active, int64_t n_failing,
                      bool constrained, int64_t max_spread, at::Tensor c1, at::Tensor cons, at::Tensor skew,
                      at::Tensor kurt, at::Tensor rel, at::Tensor qr, at::Tensor reliable, at::Tensor status,
                      bool legacy, int64_t mode, int64_t rel_dim, const c10::optional<at::Tensor>& stats) {
   exact_checks(values, c1, cons, skew, kurt, rel, qr, reliable, status);
   TORCH_CHECK(mode >= 0 && mode <= 2, "mode: 0 (whole round), 1 / 2 (D-sharded halves)");
-  ExactParams p{};
-  p.legacy = legacy ? 1 : 0;
-  p.mode = (int)mode;
-  p.rel_dim = (int)rel_dim;
-  p.values = values.data_ptr();
-  p.val32 = values.scalar_type() == at::kInt ? 1 : 0;
-  p.B = (int)values.size(0); p.N = (int)values.size(1); p.D = (int)values.size(2);
-  TORCH_CHECK(p.N >= 1 && p.N <= kExactMaxN, "GPU exact path supports N <= ", kExactMaxN);
-  p.active = active_ptr(active, p.B, values.device());
-  p.n_failing = (int)n_failing;
-  p.constrained = constrained ? 1 : 0;
-  p.max_spread = max_spread;
+  ExactLaunch l(values, active, n_failing, constrained, max_spread, legacy, mode, rel_dim, stats);
+  ExactParams& p = l.p;
   at::Tensor c1_stage;   // whole rounds: c1 staged, committed where the round succeeded (as fast_round_hip)
   if (mode == 0) c1_stage = at::empty_like(c1);
   p.c1 = mode == 0 ? c1_stage.data_ptr<int64_t>() : c1.data_ptr<int64_t>();
@@ -377,34 +429,7 @@ void exact_round_hip(const at::Tensor& values, const c10::optional<at::Tensor>& 
   p.qr = qr.data_ptr<int64_t>();
   p.reliable = reliable.data_ptr<uint8_t>();
   p.status = status.data_ptr<int32_t>();
-  if (stats.has_value() && stats->defined()) {
-    // [0] += rounds the wide-column unconstrained kernel committed, [1] += rounds left to the i128 kernel
-    TORCH_CHECK(stats->scalar_type() == at::kInt && stats->numel() >= 2 && stats->device() == values.device(),
-                "stats: int32 [>= 2] on the values' device");
-    p.xstats = (unsigned int*)stats->data_ptr();
-  }
-  at::Tensor work;
-  if ((int64_t)p.D * kExactWsCols * 8 > 64 * 1024) {  // wide instances: per-column intermediates in HBM
-    work = at::empty({(int64_t)p.B, kExactWsCols, (int64_t)p.D}, values.options().dtype(at::kLong));
-    p.work = work.data_ptr<int64_t>();
-  }
-  // column-parallel kernel (consensus_wsad.hip), the i128 kernel for the instances it flags;
-  // SVOC_EXACT_I128=1 forces the i128 kernel everywhere (tests, A/B)
-  at::Tensor stage, fallback;
-  const char* force = std::getenv("SVOC_EXACT_I128");
-  if (p.N >= 4 && !(force && force[0] == '1')) {
-    p.win_h = mode == 0 && constrained && !legacy ? exact_win_h(p.N, p.n_failing) : 0;
-    // (c1, consensus, skewness, kurtosis; the window keys; unconstrained: the columns' base words)
-    stage = at::empty({(int64_t)p.B, 4 + 2 * p.win_h + (constrained ? 0 : 2), (int64_t)p.D},
-                      values.options().dtype(at::kInt));
-    fallback = at::empty({(int64_t)p.B}, values.options().dtype(at::kByte));
-    p.stage = stage.data_ptr<int32_t>();
-    p.fallback = fallback.data_ptr<uint8_t>();
-    const char* only = std::getenv("SVOC_EXACT_WSAD_ONLY");
-    p.skip_fallback = only && only[0] == '1';
-    const char* md = std::getenv("SVOC_EXACT_WSAD_MIN_D");   // tests: route small instances through it too
-    p.wsad_min_d = md ? std::atoi(md) : 64;
-  }
+  if (l.column_kernel(values)) l.alloc_stage(values);
   auto stream = c10::hip::getCurrentHIPStream(values.device().index()).stream();
   const int rc = svoc_exact_round(&p, stream);
   TORCH_CHECK(rc == 0, "svoc_exact_round launch failed: ", rc);
@@ -412,6 +437,68 @@ void exact_round_hip(const at::Tensor& values, const c10::optional<at::Tensor>& 
     const int rc2 = svoc_commit_rows(c1_stage.data_ptr(), c1.data_ptr(), p.status, p.active, p.B, 2 * (int64_t)p.D, stream);
     TORCH_CHECK(rc2 == 0, "svoc_commit_rows failed: ", rc2);
   }
+}
+
+// ---- exact_verdict: the status (and rel where it is OK) of the round exact_round would compute; no other output
+void verdict_checks(const at::Tensor& values, const at::Tensor& rel, const at::Tensor& status) {
+  TORCH_CHECK(values.dim() == 3 && (values.scalar_type() == at::kLong || values.scalar_type() == at::kInt) &&
+                  values.is_contiguous(),
+              "values: contiguous int64 or int32 [B, N, D] wsad");
+  check_out(rel, at::kLong, {values.size(0), 2}, "rel", values.device());
+  check_out(status, at::kInt, {values.size(0)}, "status", values.device());
+}
+
+// the outputs a verdict throws away: c1, consensus, skewness, kurtosis [B, D], qr [B, N], reliable [B, N]
+struct ScratchOutputs {
+  at::Tensor cols, qr, reliable;
+  explicit ScratchOutputs(const at::Tensor& values) {
+    const int64_t B = values.size(0), N = values.size(1), D = values.size(2);
+    cols = at::empty({4, B, D}, values.options().dtype(at::kLong));
+    qr = at::empty({B, N}, values.options().dtype(at::kLong));
+    reliable = at::empty({B, N}, values.options().dtype(at::kByte));
+  }
+};
+
+void exact_verdict_cpu(const at::Tensor& values, const c10::optional<at::Tensor>& active, int64_t n_failing,
+                       bool constrained, int64_t max_spread, at::Tensor rel, at::Tensor status, bool legacy,
+                       const c10::optional<at::Tensor>& stats, const c10::optional<at::Tensor>& vstats) {
+  (void)vstats;   // (GPU kernel routing counters; the CPU engine is one path)
+  verdict_checks(values, rel, status);
+  // the full round into scratch outputs: it writes status where the instance is active and rel where the round
+  // succeeded, like every other output
+  ScratchOutputs o(values);
+  exact_round_cpu(values, active, n_failing, constrained, max_spread, o.cols[0], o.cols[1], o.cols[2], o.cols[3], rel,
+                  o.qr, o.reliable, status, legacy, 0, 0, stats);
+}
+
+void exact_verdict_hip(const at::Tensor& values, const c10::optional<at::Tensor>& active, int64_t n_failing,
+                       bool constrained, int64_t max_spread, at::Tensor rel, at::Tensor status, bool legacy,
+                       const c10::optional<at::Tensor>& stats, const c10::optional<at::Tensor>& vstats) {
+  verdict_checks(values, rel, status);
+  ExactLaunch l(values, active, n_failing, constrained, max_spread, legacy, 0, 0, stats);
+  ExactParams& p = l.p;
+  p.rel = rel.data_ptr<int64_t>();
+  p.status = status.data_ptr<int32_t>();
+  if (vstats.has_value() && vstats->defined()) {
+    TORCH_CHECK(vstats->scalar_type() == at::kInt && vstats->numel() >= 3 && vstats->device() == values.device() &&
+                    vstats->is_contiguous(),
+                "vstats: contiguous int32 [3] on the values' device");
+    p.vstats = (unsigned int*)vstats->data_ptr();
+  }
+  // the outputs nobody reads: the instances the verdict kernel flags, and every shape it does not take, run the
+  // full round into them (c1 straight into its buffer: nothing to stage for a throw-away row)
+  ScratchOutputs o(values);
+  p.c1 = o.cols[0].data_ptr<int64_t>();
+  p.consensus = o.cols[1].data_ptr<int64_t>();
+  p.skew = o.cols[2].data_ptr<int64_t>();
+  p.kurt = o.cols[3].data_ptr<int64_t>();
+  p.qr = o.qr.data_ptr<int64_t>();
+  p.reliable = o.reliable.data_ptr<uint8_t>();
+  // (the verdict form has no stage; every other shape runs the full column kernel with its own)
+  if (l.column_kernel(values) && !svoc_exact_verdict_applies(&p)) l.alloc_stage(values);
+  auto stream = c10::hip::getCurrentHIPStream(values.device().index()).stream();
+  const int rc = svoc_exact_verdict(&p, stream);
+  TORCH_CHECK(rc == 0, "svoc_exact_verdict launch failed: ", rc);
 }
 
 }  // namespace
@@ -430,17 +517,22 @@ TORCH_LIBRARY(svoc, m) {
       "Tensor(a!) c1, Tensor(b!) consensus, Tensor(c!) skew, Tensor(d!) kurt, Tensor(e!) rel, Tensor(f!) qr, "
       "Tensor(g!) reliable, Tensor(h!) status, bool legacy=False, int mode=0, int rel_dim=0, "
       "Tensor(i!)? stats=None) -> ()");
+  m.def(
+      "exact_verdict(Tensor values, Tensor? active, int n_failing, bool constrained, int max_spread, "
+      "Tensor(a!) rel, Tensor(b!) status, bool legacy, Tensor(c!)? stats=None, Tensor(d!)? vstats=None) -> ()");
   svoc::register_extra_defs(m);
 }
 
 TORCH_LIBRARY_IMPL(svoc, CPU, m) {
   m.impl("fast_round", &svoc::fast_round_cpu);
   m.impl("exact_round", &svoc::exact_round_cpu);
+  m.impl("exact_verdict", &svoc::exact_verdict_cpu);
   svoc::register_extra_cpu(m);
 }
 
 TORCH_LIBRARY_IMPL(svoc, CUDA, m) {
   m.impl("fast_round", &svoc::fast_round_hip);
   m.impl("exact_round", &svoc::exact_round_hip);
+  m.impl("exact_verdict", &svoc::exact_verdict_hip);
   svoc::register_extra_hip(m);
 }

@@ -126,6 +126,10 @@ struct ExactParams {
   // [2] or null: += rounds committed by the wide-column unconstrained kernel (consensus_wsadx.hip), += rounds
   // left to the i128 kernel
   unsigned int* xstats;
+  // verdict rounds (svoc_exact_verdict): uint32 [3] or null: [0] += rounds the verdict form of the column kernel
+  // judged, [1] += rounds handed to the full-round path; [2] belongs to the engine (final rounds of a
+  // verdict-wave step that did not come out OK: ConsensusEngine.verdict_routing) and is not written here
+  unsigned int* vstats;
 };
 
 // Window half-width of the column-parallel exact kernel's one-network path (consensus_wsad.hip): the
@@ -148,6 +152,11 @@ int svoc_fast_round_bf16(const svoc::FastParams* p, hipStream_t stream);
 int svoc_fast_round_f32(const svoc::FastParams* p, hipStream_t stream);   // values fp32 [B, N, ld]
 int svoc_fast_round_f32_win(const svoc::FastParams* p, hipStream_t stream);
 int svoc_exact_round(const svoc::ExactParams* p, hipStream_t stream);
+// Verdict of a whole round: status, and rel where it is OK; no other output is produced where the verdict form
+// of the column kernel applies (svoc_exact_verdict_applies: the caller then passes `fallback` and no `stage`).
+// Everything else runs svoc_exact_round into the output buffers of `p` (throw-away ones of the caller).
+int svoc_exact_verdict(const svoc::ExactParams* p, hipStream_t stream);
+int svoc_exact_verdict_applies(const svoc::ExactParams* p);
 }
 
 namespace svoc {

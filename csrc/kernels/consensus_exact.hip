@@ -463,3 +463,40 @@ extern "C" int svoc_exact_round(const ExactParams* p, hipStream_t stream) {
   }
   return exact_round_i128(p, stream);
 }
+
+extern "C" int svoc_exact_verdict_wsad(const ExactParams* p, hipStream_t stream);
+
+namespace svoc {
+// rounds of a verdict call that take the full-round path as a whole: vstats[1] += active instances
+__global__ __launch_bounds__(256) void verdict_handoff_count_kernel(const uint8_t* active, int B, unsigned int* vstats) {
+  unsigned int n = 0;
+  for (int b = threadIdx.x; b < B; b += 256) n += (!active || active[b]) ? 1u : 0u;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) n += __shfl_xor(n, o);
+  if ((threadIdx.x & 63) == 0 && n) atomicAdd(&vstats[1], n);
+}
+}  // namespace svoc
+
+// Exact verdict: status (and rel where it is OK) of the round svoc_exact_round would compute.  Where the verdict
+// form of the column kernel applies (the caller passes `fallback` and no `stage`) it judges every instance it
+// can, and only the ones it flags run the i128 kernel, as after the full column kernel; every other shape or
+// config runs svoc_exact_round as it is.  Both write the outputs of *p, which the caller throws away.
+extern "C" int svoc_exact_verdict(const ExactParams* p, hipStream_t stream) {
+  if (p->B <= 0) return 0;
+  if (p->N < 1 || p->N > kExactMaxN || p->D < 1) return -1;
+  if (p->fallback && !p->stage) {
+    const int rc = svoc_exact_verdict_wsad(p, stream);
+    if (rc != -2) {
+      if (rc != 0 || p->skip_fallback) return rc;
+      ExactParams q = *p;
+      q.active = p->fallback;
+      return exact_round_i128(&q, stream);
+    }
+  }
+  if (p->vstats) {
+    hipLaunchKernelGGL(verdict_handoff_count_kernel, dim3(1), dim3(256), 0, stream, p->active, p->B, p->vstats);
+    const int rc = (int)hipGetLastError();
+    if (rc != 0) return rc;
+  }
+  return svoc_exact_round(p, stream);
+}

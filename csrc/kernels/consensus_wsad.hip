@@ -269,7 +269,12 @@ SVOC_DEV T group_sum(T v) {
 // g_{r+j} has at least r + 1 elements of A at or below it).  Ranks R/2 - 1 and R/2 (math.cairo:113-126)
 // need g at positions R/2 - 1 .. R/2 + f, inside the window when WINH >= max(a + 1, f - a + 1),
 // a = N/2 - R/2.  The second network over the reliable rows (~30 % of the kernel's VALU) goes away.
-template <int NSEG, int WAVES, bool V32, int MODE, bool CONS, int WINH = 0>
+// VERDICT (whole constrained non-legacy rounds, NSEG <= 4, no window): accept or revert, without the outputs.
+// After rel1, the rank cut, rel2 and R < 4 the moments fail only by a division by zero (a reliable column of
+// variance 0 or 1), so pass 2 keeps the reliable mean and variance of every column and nothing else: no second
+// median, no z-powers, no staging and no commit.  Written: status, rel where it is OK, fallback, and p.vstats
+// (a flagged round also counts in p.xstats[1], as the full round's hand-off does).
+template <int NSEG, int WAVES, bool V32, int MODE, bool CONS, int WINH = 0, bool VERDICT = false>
 // (2 waves per SIMD where the kernel fits 256 VGPRs without scratch in its loops: the whole / first-half constrained
 // rounds and the unconstrained int64 ones; the unconstrained int32 and D-sharded second-half instantiations spill
 // a few hundred bytes at that cap and keep one wave with AGPR spill slots)
@@ -277,6 +282,7 @@ __global__ __launch_bounds__(WAVES * 64)
 __attribute__((amdgpu_waves_per_eu(NSEG <= 4 && !(CONS && MODE == 2) ? 2 : 1)))
 void consensus_wsad_kernel(ExactParams p) {
   static_assert(WINH == 0 || (MODE == 0 && CONS), "the window path is for whole constrained rounds");
+  static_assert(!VERDICT || (MODE == 0 && CONS && WINH == 0 && NSEG <= 4), "verdicts: whole constrained rounds");
   constexpr int P = 64 / NSEG;      // columns per wave
   constexpr int NPAD = 64 * NSEG;   // padded oracle rows
   constexpr int W = WAVES * P;      // columns per tile
@@ -325,6 +331,13 @@ void consensus_wsad_kernel(ExactParams p) {
     early_st = ST_OK;
     div0 = 0;
   }
+  // verdict form: the routing counters (thread 0, once per round): 0 judged here, 1 handed off
+  auto count_verdict = [&](int which) __attribute__((always_inline)) {
+    if constexpr (VERDICT) {
+      if (p.vstats) atomicAdd(&p.vstats[which], 1u);
+      if (which == 1 && p.xstats) atomicAdd(&p.xstats[1], 1u);
+    }
+  };
   const int seg = lane / P, cw = lane % P;
   const int N = p.N, D = p.D;
   const int rowb = D * ESZ;
@@ -507,7 +520,7 @@ void consensus_wsad_kernel(ExactParams p) {
         c1 = (uint32_t)(int32_t)tdiv_rel_fix(sum / 2, (sum & 1) == 0, sum < 0, (int64_t)(((uint64_t)Bh << 32) | Bl));
       }
     }
-    if (seg == 0 && vc) {
+    if (!VERDICT && seg == 0 && vc) {
       stg[col] = (int32_t)c1;
       if constexpr (!CONS) {
         stg[4 * D + col] = (int32_t)Bl;
@@ -659,7 +672,10 @@ void consensus_wsad_kernel(ExactParams p) {
   if (MODE != 2 && badv) flag = 1;
   __syncthreads();
   if (MODE == 0 && flag) {   // a value outside the domain: the wide-column / i128 kernels take the round (pass 1
-    if (tid == 0) p.fallback[b] = 1;   // stopped at the wave's first such slab; no rank mask / reliabilities here)
+    if (tid == 0) {                    // stopped at the wave's first such slab; no rank mask / reliabilities here)
+      p.fallback[b] = 1;
+      count_verdict(1);
+    }
     return;
   }
   if (MODE == 1) {   // first half done: c1 and the qr partials out (partials < 2^58: D <= 2^38 columns)
@@ -767,13 +783,17 @@ void consensus_wsad_kernel(ExactParams p) {
   if (badv) flag = 1;
   __syncthreads();
   if (flag) {
-    if (tid == 0) p.fallback[b] = 1;
+    if (tid == 0) {
+      p.fallback[b] = 1;
+      count_verdict(1);
+    }
     return;
   }
   if (early_st != ST_OK) {   // reverted before the moments: final, outputs untouched
     if (tid == 0) {
       p.status[b] = early_st;
       p.fallback[b] = 0;
+      count_verdict(0);
     }
     return;
   }
@@ -842,7 +862,9 @@ void consensus_wsad_kernel(ExactParams p) {
     asm volatile("" : "+v"(mm), "+v"(ml));   // keep the 64 row masks out of the slab loop's live set
     uint32_t cons = 0;
     if constexpr (TILE) load_tile(s);
-    if constexpr (CONS && WINH > 0) {
+    if constexpr (VERDICT) {
+      // (no pass-2 median: the verdict needs the reliable mean and variance only)
+    } else if constexpr (CONS && WINH > 0) {
       cons = (uint32_t)stg[D + (vc ? col : 0)];   // (the window phase above)
     } else if constexpr (CONS) {
       uint32_t r[64];
@@ -875,7 +897,7 @@ void consensus_wsad_kernel(ExactParams p) {
       cons = (lo + hi) >> 1;
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (CONS && p.legacy) {   // (uniform) obsolete contracts: consensus only, no moments stored
+    if (!VERDICT && CONS && p.legacy) {   // (uniform) obsolete contracts: consensus only, no moments stored
       if (seg == 0 && vc) {
         stg[D + col] = (int32_t)cons;
         stg[2 * D + col] = 0;
@@ -998,6 +1020,7 @@ void consensus_wsad_kernel(ExactParams p) {
       sd = (double)sdi;
     }
     if (vc && !ok_sd) dz = true;   // sqrt(0) -> wsad_div by 0, sqrt(1) divides by 0: DIV_BY_ZERO
+    if constexpr (VERDICT) continue;   // (the z-powers and the moments' arithmetic cannot fail otherwise)
     // z = wsad_div(x - mu, sd) = I128Div((x - mu) 1e6 + floor(sd / 2), sd): A = x 1e6 + C0 (exact integers
     // below 2^51), then the half-offset forms of wsad_fast.hpp -- no remainder tests in the row loop
     const double isd = 1.0 / sd, hisd = 0.5 * isd;
@@ -1093,13 +1116,27 @@ void consensus_wsad_kernel(ExactParams p) {
   if (dz) div0 = 1;
   __syncthreads();
   if (flag) {
-    if (tid == 0) p.fallback[b] = 1;
+    if (tid == 0) {
+      p.fallback[b] = 1;
+      count_verdict(1);
+    }
     return;
   }
   if (div0) {   // (every moment failure is DIV_BY_ZERO, whichever column comes first: final)
     if (tid == 0) {
       p.status[b] = ST_DIV_BY_ZERO;
       p.fallback[b] = 0;
+      count_verdict(0);
+    }
+    return;
+  }
+  if constexpr (VERDICT) {   // accepted: the reliabilities only
+    if (tid == 0) {
+      p.rel[2 * (int64_t)b] = rels[0];
+      p.rel[2 * (int64_t)b + 1] = rels[1];
+      p.status[b] = ST_OK;
+      p.fallback[b] = 0;
+      count_verdict(0);
     }
     return;
   }
@@ -1164,6 +1201,14 @@ template <int NSEG>
 static int launch_wsad(const ExactParams& p, hipStream_t stream) {
   return p.constrained ? launch_wsad_c<NSEG, true>(p, stream) : launch_wsad_c<NSEG, false>(p, stream);
 }
+template <int NSEG>
+static int launch_verdict(const ExactParams& p, hipStream_t stream) {
+  constexpr int WAVES = 4;
+  auto k = p.val32 ? consensus_wsad_kernel<NSEG, WAVES, true, 0, true, 0, true>
+                   : consensus_wsad_kernel<NSEG, WAVES, false, 0, true, 0, true>;
+  hipLaunchKernelGGL(k, dim3(p.B), dim3(WAVES * 64), 0, stream, p);
+  return (int)hipGetLastError();
+}
 
 }  // namespace svoc
 
@@ -1187,4 +1232,25 @@ extern "C" int svoc_exact_round_wsad(const ExactParams* p, hipStream_t stream) {
   if (p->N <= 1024) return launch_wide<16>(*p, stream);
   if (p->N <= 2048) return launch_wide<32>(*p, stream);
   return launch_wide<64>(*p, stream);
+}
+
+// Whether the verdict form takes the rounds of *p: the guards above (the stage aside: it has none), and whole
+// constrained non-legacy rounds of N <= 256 oracles.  ConsensusEngine._verdict_ok (svoc/engine.py) states the same
+// conditions to choose verdict waves for the exact stream: keep the two in step (where they differ the results stay
+// right -- the op takes the full-round path -- but every wave then pays a full round).
+extern "C" int svoc_exact_verdict_applies(const ExactParams* p) {
+  if (p->N < 4 || p->N > 256) return 0;
+  if (p->mode != 0 || !p->constrained || p->legacy) return 0;
+  if (p->N <= 32 && p->D < p->wsad_min_d) return 0;
+  if ((int64_t)p->N * p->D * (p->val32 ? 4 : 8) >= (1ll << 31)) return 0;   // 32-bit buffer offsets
+  return 1;
+}
+
+// -2: not applicable (the caller runs the full round).
+extern "C" int svoc_exact_verdict_wsad(const ExactParams* p, hipStream_t stream) {
+  if (p->B <= 0) return 0;
+  if (!p->fallback || !svoc_exact_verdict_applies(p)) return -2;
+  if (p->N <= 64) return launch_verdict<1>(*p, stream);
+  if (p->N <= 128) return launch_verdict<2>(*p, stream);
+  return launch_verdict<4>(*p, stream);
 }

@@ -35,6 +35,16 @@ class ConsensusService:
     def update_predictions(self, items: Sequence[Tuple[int, int, Sequence]]) -> List[Status]:
         """items: (instance, caller_address, prediction).  Predictions are wsad ints (exact mode)
         or floats (fast mode).  Returns one status per item (reverts do not raise)."""
+        return self._predictions(items, self.engine.step)
+
+    def preview_predictions(self, items: Sequence[Tuple[int, int, Sequence]]) -> List[Status]:
+        """The statuses :meth:`update_predictions` would return for ``items``, with nothing changed (exact mode;
+        :meth:`ConsensusEngine.preview_updates`)."""
+        if self.engine.mode != "exact":
+            raise NotImplementedError("preview needs exact mode (mode='exact')")
+        return self._predictions(items, self.engine.preview_updates)
+
+    def _predictions(self, items, run) -> List[Status]:
         pre, cand = [], []
         for k, (b, caller, pred) in enumerate(items):
             if len(pred) != self.cfg.dimension:
@@ -62,7 +72,7 @@ class ConsensusService:
             out[k] = st
         if inst:
             dt = torch.int64 if self.engine.mode == "exact" else torch.float32
-            st = self.engine.step(torch.tensor(inst), torch.tensor(orc), torch.tensor(vals, dtype=dt))
+            st = run(torch.tensor(inst), torch.tensor(orc), torch.tensor(vals, dtype=dt))
             it = iter(st.cpu().tolist())
             for k in range(len(items)):
                 if all(k != p for p, _ in pre):
@@ -81,6 +91,12 @@ class ConsensusService:
         work and no device->host copy beyond what ``step`` itself does."""
         inst = torch.as_tensor(inst, dtype=torch.int64, device=self.engine.device).reshape(-1)
         return self.engine.step(inst, self.gov.resolve_oracles(inst, caller), values, updates_per_instance)
+
+    def preview_batch(self, inst, caller, values, updates_per_instance: Optional[int] = None) -> torch.Tensor:
+        """:meth:`update_batch` as a simulated call: the same authentication and status order, the statuses the
+        updates would get, and no state change (:meth:`ConsensusEngine.preview_updates`; exact mode)."""
+        inst = torch.as_tensor(inst, dtype=torch.int64, device=self.engine.device).reshape(-1)
+        return self.engine.preview_updates(inst, self.gov.resolve_oracles(inst, caller), values, updates_per_instance)
 
     def governance(self, actions) -> Tuple[List[Status], List[bool]]:
         """update_proposition / vote_for_a_proposition transactions (contract.cairo:661-738).  ``actions``: a list
@@ -142,6 +158,12 @@ class OracleConsensus:
         st = self._svc.update_predictions([(self._b, caller, pred)])[0]
         self._raise(st)
         return st
+
+    def simulate_update_prediction(self, caller: int, prediction: Sequence[int]) -> Status:
+        """What ``update_prediction(caller, prediction)`` would do, without doing it (a simulated call): OK,
+        NOT_ACTIVE or the code it would revert with.  Never raises :class:`ConsensusRevert`; every getter
+        answers as before.  Exact mode."""
+        return self._svc.preview_predictions([(self._b, caller, as_wsad(prediction))])[0]
 
     def update_proposition(self, caller: int, proposition: Optional[Tuple[int, int]]) -> None:
         st, _ = self._svc.governance([("propose", self._b, caller, proposition)])
@@ -253,6 +275,10 @@ class LegacyOracleConsensus(OracleConsensus):
         st = self._svc.update_predictions([(self._b, caller, pred)])[0]
         self._raise(st)
         return st
+
+    def simulate_update_prediction(self, caller: int, prediction) -> Status:
+        vals = [int(prediction)] if self._scalar else [int(v) for v in prediction]
+        return self._svc.preview_predictions([(self._b, caller, vals)])[0]
 
     def get_consensus_value(self):
         v = self._out(self.engine.consensus[self._b])

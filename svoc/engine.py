@@ -16,7 +16,8 @@ Two numeric modes share one semantics:
   (csrc/kernels/consensus_wsad.hip) for the rounds it can prove, the i128 one
   (csrc/kernels/consensus_exact.hip) for the rest -- or the C++ CPU engine; updates are transactions
   (a reverted round rolls the update back, exactly like a reverted Starknet tx) and are replayed in
-  order per instance.
+  order per instance.  :meth:`ConsensusEngine.preview_updates` answers what a batch would return without
+  changing anything (a simulated call), with verdict rounds (``exact_verdict``: status only).
 * ``fast``: fp32 math over bf16 storage (the fused kernels csrc/kernels/consensus_fast_*.hip) or fp32
   storage (``storage="fp32"``: reference resolution, csrc/kernels/consensus_fast_f32.hip).
   Updates inside one step are coalesced (last writer wins) -- exact for the reference because a
@@ -189,6 +190,9 @@ class ConsensusEngine:
         # exact rounds on the GPU: [rounds committed by the wide-column unconstrained kernel, rounds handed to the
         # i128 kernel] (consensus_wsadx.hip; exact_routing)
         self._xstats = torch.zeros(2, dtype=torch.int32, device=dev) if (mode == "exact" and dev.type == "cuda") else None
+        # verdict rounds on the GPU (exact_verdict; verdict_routing): [judged by the verdict kernel, handed to the
+        # full-round path, final rounds of a verdict-wave step that did not come out OK (never: tests assert 0)]
+        self._vstats = torch.zeros(3, dtype=torch.int32, device=dev) if (mode == "exact" and dev.type == "cuda") else None
         self._pending = _PendingBatches(self)
         self._save_bufs: Dict[tuple, tuple] = {}
         # health counters folded in by every round's epilogue: [rel2 sum (2^-32 units fast / wsad
@@ -552,6 +556,35 @@ class ConsensusEngine:
         x = self._xstats.tolist()
         return {"processed": processed, "wide_column": int(x[0]), "i128": int(x[1])}
 
+    def verdict_routing(self) -> Dict[str, int]:
+        """Exact engine on the GPU: the verdict rounds so far (the transaction waves of the strided stream,
+        :meth:`_verdict_ok`) -- ``verdict`` judged by the verdict form of the column kernel, ``fallback`` handed
+        to the full-round path, and ``mismatch``: final rounds of a verdict-wave step that did not come out OK
+        although a wave had accepted (must stay 0)."""
+        self.pipeline_join()
+        if self._vstats is None:
+            return {"verdict": 0, "fallback": 0, "mismatch": 0}
+        v = self._vstats.tolist()
+        return {"verdict": int(v[0]), "fallback": int(v[1]), "mismatch": int(v[2])}
+
+    def _verdict_ok(self) -> bool:
+        """Whether the strided exact stream judges its waves with verdict rounds and computes the outputs once
+        per step: the GPU, and the shapes and configs the verdict form of the column kernel takes (whole
+        constrained non-legacy rounds, 4 <= N <= 256, the column kernel's own guards: svoc_exact_verdict_applies).
+        ``SVOC_VERDICT_WAVES=0`` selects one full round per wave (A/B).
+
+        These conditions must match ``svoc_exact_verdict_applies`` (csrc/kernels/consensus_wsad.hip) and the
+        switches the binding reads (``SVOC_EXACT_I128``, ``SVOC_EXACT_WSAD_MIN_D``): where they differ the results
+        stay right, since ``exact_verdict`` then runs full rounds, but every wave pays one."""
+        if os.environ.get("SVOC_VERDICT_WAVES", "1") == "0":
+            return False
+        if os.environ.get("SVOC_EXACT_I128", "0")[:1] == "1":
+            return False
+        min_d = int(os.environ.get("SVOC_EXACT_WSAD_MIN_D", "64"))
+        return (self.mode == "exact" and self.device.type == "cuda" and self.cfg.constrained
+                and not self.cfg.legacy and 4 <= self.N <= 256 and not (self.N <= 32 and self.D < min_d)
+                and self.N * self.D * self.values.element_size() < (1 << 31))
+
     def metrics(self) -> torch.Tensor:
         """[sum rel2 of committed rounds, committed, processed, reverted] as float64 (device)."""
         self.pipeline_join()
@@ -576,6 +609,27 @@ class ConsensusEngine:
             return st
         return self._exact_transactions(inst, oracle, vals, updates_per_instance)
 
+    def preview_updates(self, inst, oracle, vals, updates_per_instance: Optional[int] = None) -> torch.Tensor:
+        """The statuses :meth:`step` would return for this batch in exact mode, with no state change (a
+        simulated call): transactions are sequential per instance, so an accepted earlier update of the batch
+        is visible to a later one and a reverted one is not.  Each wave stores its rows, a verdict round
+        (``exact_verdict``: status only) judges it and the reverted rows go back; after the last wave every
+        stored row, ``enabled`` flag and ``n_active`` is put back, newest wave first.  Extra memory: the rows
+        the batch overwrites."""
+        self.pipeline_join()
+        if self.mode != "exact":
+            raise NotImplementedError("preview_updates needs exact mode (mode='exact'): a fast-mode step coalesces "
+                                      "its batch into one round")
+        return self._exact_transactions(inst, oracle, vals, updates_per_instance, commit=False)
+
+    def _verdict_round(self, active: torch.Tensor, rel: torch.Tensor, status: torch.Tensor, count: bool) -> None:
+        """Prologue + exact_verdict over the touched, fully active instances: ``status`` and (where OK) ``rel``.
+        ``count``: advance the routing counters as a full round would (a preview leaves them alone)."""
+        self._ops.round_prologue(self.n_active, self.touched, self.N, True, active)
+        self._ops.exact_verdict(self.values, active, self.cfg.n_failing_oracles, self.cfg.constrained,
+                                self.cfg.max_spread_wsad, rel, status, self.cfg.legacy,
+                                self._xstats if count else None, self._vstats if count else None)
+
     def _transaction_waves(self, inst: torch.Tensor, oracle: torch.Tensor):
         """Device-side grouping of a batch into transaction waves: wave k = the k-th valid update of every
         instance (batch order kept per instance).  Returns (order, bounds): the update indices sorted by
@@ -597,13 +651,16 @@ class ConsensusEngine:
         bounds = [0] + torch.cumsum(counts[:n_waves], 0).tolist()
         return order, bounds
 
-    def _exact_transactions(self, inst, oracle, vals, updates_per_instance: Optional[int] = None) -> torch.Tensor:
+    def _exact_transactions(self, inst, oracle, vals, updates_per_instance: Optional[int] = None,
+                            commit: bool = True) -> torch.Tensor:
         """Sequential per-update transactions (contract.cairo:588-603: update_prediction stores the row,
         then the full consensus round; a round that fails reverts the whole transaction), replayed as
         waves: wave k applies the k-th update of every instance at once -- instances are independent,
         so this is the per-instance sequential order.  Everything stays on the device: per wave one
         gather of the old rows, the batched store, the round over the touched instances and a masked
-        restore for the transactions whose round failed."""
+        restore for the transactions whose round failed.
+        ``commit=False`` (:meth:`preview_updates`): the rounds are verdicts into scratch tensors with no
+        epilogue, and the accepted rows are put back after the last wave."""
         inst = torch.as_tensor(inst, dtype=torch.int64, device=self.device).reshape(-1)
         oracle = torch.as_tensor(oracle, dtype=torch.int64, device=self.device).reshape(-1)
         vals = self._as_storage(torch.as_tensor(vals))
@@ -626,7 +683,7 @@ class ConsensusEngine:
                 if not bool((lay | ~okl).all()):
                     K = 0
             if K and self.device.type == "cuda":
-                return self._exact_transactions_k(inst, oracle, vals, K, out)
+                return self._exact_transactions_k(inst, oracle, vals, K, out, commit)
             waves = [torch.arange(k, U, K, device=self.device) for k in range(K)]
         else:
             order, bounds = self._transaction_waves(inst, oracle)
@@ -634,6 +691,10 @@ class ConsensusEngine:
             if bounds[-1] < U:   # unknown instance / oracle: status only (interval check first), no store
                 bad = order[bounds[-1]:]
                 out[bad] = self.apply_updates(inst[bad], oracle[bad], vals[bad])
+        if not commit:
+            touched0 = self.touched.clone()
+            p_active, p_rel, p_status = self._active.clone(), self.rel.clone(), self.status.clone()
+            undo = []
         for sel in waves:
             bi, oi = inst[sel], oracle[sel]
             if K:
@@ -651,8 +712,13 @@ class ConsensusEngine:
             old_na = self.n_active[bi_c].clone()
             self.touched.zero_()
             st_u = self.apply_updates(bi, oi, vals[sel])
-            self.run_round(only_touched=True)        # outputs are only written when a round succeeds
-            st_b = self.status[bi_c]
+            if commit:
+                self.run_round(only_touched=True)    # outputs are only written when a round succeeds
+                st_b = self.status[bi_c]
+            else:
+                self._verdict_round(p_active, p_rel, p_status, count=False)
+                st_b = p_status[bi_c]
+                undo.append((bi_c, oi_c, old_rows, old_en, old_na))
             full = self.n_active[bi_c] == self.N
             tx = torch.where(st_u != 0, st_u,
                              torch.where(full, st_b, torch.full_like(st_b, int(Status.NOT_ACTIVE))))
@@ -664,29 +730,90 @@ class ConsensusEngine:
             self.enabled[bi_c, oi_c] = torch.where(revert, old_en, self.enabled[bi_c, oi_c])
             self.n_active[bi_c] = torch.where(revert, old_na, self.n_active[bi_c])
             out[sel] = tx
+        if not commit:
+            # the accepted (and the stored, not yet active) rows go back, newest wave first; a row its wave did
+            # not change gets the value it has
+            for bi_c, oi_c, old_rows, old_en, old_na in reversed(undo):
+                self.values[bi_c, oi_c] = old_rows
+                self.enabled[bi_c, oi_c] = old_en
+                self.n_active[bi_c] = old_na
+            self.touched.copy_(touched0)
         return out
 
-    def _exact_transactions_k(self, inst, oracle, vals, K: int, out: torch.Tensor) -> torch.Tensor:
+    def _exact_transactions_k(self, inst, oracle, vals, K: int, out: torch.Tensor, commit: bool = True) -> torch.Tensor:
         """_exact_transactions for the b * K + k layout on the GPU, with the transaction bookkeeping in the update
         and restore kernels: per wave the update kernel validates, saves the overwritten row / ``enabled`` flag
         and stores (one launch), the round runs, and the restore kernel rolls back the transactions whose round
         reverted and gives every applied update its transaction status -- the round's code, NOT_ACTIVE where the
         instance is not fully active (the update stays stored), OK otherwise.  The per-wave gathers, compares,
         ``where`` selects and scatters of the general path (~20 small kernels, ~10 % of a c3 wave) go away; the
-        batch is reordered wave-major once."""
+        batch is reordered wave-major once.
+
+        Verdict waves (:meth:`_verdict_ok`): an accepted round overwrites every output in full, so of a step's
+        rounds only the last accepted one of an instance is visible in the outputs -- the waves need the verdict
+        alone (``exact_verdict``: status, rel for the epilogue's counters), and one full round after the last
+        wave, over the instances that accepted any, computes the outputs from the rows that round left: later
+        transactions of the instance reverted or were rejected, so the rows are the ones it saw.
+
+        ``commit=False`` (:meth:`preview_updates`): verdicts into scratch tensors, no epilogue, every wave keeps
+        its saved rows, and after the last wave they all go back, newest wave first."""
         n = inst.numel() // K
         iw = inst.view(n, K).t().contiguous()                 # [K, n]: wave k = the k-th update of every instance
         ow = oracle.view(n, K).t().contiguous()
         vw = vals.reshape(n, K, -1).transpose(0, 1).contiguous()
         sw = torch.empty(K, n, dtype=torch.int32, device=self.device)
+        if not commit:
+            return self._preview_k(iw, ow, vw, sw, out)
         sv, sen, _ = self._save_buffer(("exact_tx",), n)
+        verdict = self._verdict_ok()
+        mx = self.cfg.max_spread_wsad
+        if verdict:
+            accepted = torch.zeros(self.B, dtype=torch.uint8, device=self.device)   # a wave ran and came out OK
         for k in range(K):
             self.touched.zero_()
             self.apply_updates(iw[k], ow[k], vw[k], unique=True, save=(sv, sen, sw[k]))
-            self.run_round(only_touched=True)                 # outputs are only written when a round succeeds
+            if verdict:
+                self._verdict_round(self._active, self.rel, self.status, count=True)
+                self._ops.round_epilogue(self._active, self.status, self.rel, self.consensus_active, self.touched,
+                                         self.metrics_fx)
+                accepted |= torch.where(self.status == int(Status.OK), self._active, 0)
+                self.rounds += 1
+            else:
+                self.run_round(only_touched=True)             # outputs are only written when a round succeeds
             self._ops.restore_updates(self.values, self.enabled, self.n_active, iw[k], ow[k], sw[k], sv, sen,
                                       self.status, self._active, int(Status.NOT_ACTIVE))
+        if verdict:
+            # the outputs, once: the round of each instance's last accepted transaction
+            final = torch.zeros_like(self.status)
+            self._ops.exact_round(self.values, accepted, self.cfg.n_failing_oracles, self.cfg.constrained, mx,
+                                  self.c1, self.consensus, self.skew, self.kurt, self.rel, self.qr, self.reliable,
+                                  final, self.cfg.legacy)
+            self._vstats[2:3] += ((accepted != 0) & (final != int(Status.OK))).sum().to(torch.int32)
         out.copy_(sw.t().reshape(-1))
+        return out
+
+    def _preview_k(self, iw, ow, vw, sw, out: torch.Tensor) -> torch.Tensor:
+        """The waves of :meth:`_exact_transactions_k` without committing anything (preview_updates)."""
+        K, n = iw.shape
+        sv = torch.empty(K, n, self.D, dtype=self.vdtype, device=self.device)
+        sen = torch.empty(K, n, dtype=torch.uint8, device=self.device)
+        touched0 = self.touched.clone()
+        active, rel, status = self._active.clone(), self.rel.clone(), self.status.clone()
+        for k in range(K):
+            self.touched.zero_()
+            self.apply_updates(iw[k], ow[k], vw[k], unique=True, save=(sv[k], sen[k], sw[k]))
+            self._verdict_round(active, rel, status, count=False)
+            self._ops.restore_updates(self.values, self.enabled, self.n_active, iw[k], ow[k], sw[k], sv[k], sen[k],
+                                      status, active, int(Status.NOT_ACTIVE))
+        out.copy_(sw.t().reshape(-1))
+        # what is still stored (accepted, or stored into a not yet active instance) goes back, newest wave first
+        status.fill_(int(Status.DIV_BY_ZERO))   # (any revert code: restore_updates rolls back where it is not OK)
+        active.fill_(1)
+        for k in reversed(range(K)):
+            stored = torch.where(sw[k] == int(Status.NOT_ACTIVE), 0, sw[k])
+            self._ops.restore_updates(self.values, self.enabled, self.n_active, iw[k], ow[k], stored, sv[k], sen[k],
+                                      status, active)
+        self.touched.copy_(touched0)
         return out
 
     # ------------------------------------------------------------------ synthetic data
