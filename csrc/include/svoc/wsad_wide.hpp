@@ -115,4 +115,50 @@ SVOC_HD void skew_kurt_x(double s3, double s4, double Rd, double& sk, double& ku
   ku = trunc_div_d(t1 - t2, k4d, ik4);
 }
 
+// ---- Up to 256 reliable rows (consensus_wsadx_groups.hip: lane groups of 2 / 4, 64 < N <= 256) ---------------------
+// The routines above that work on one row (qdev_dd, wdiv_z, wdiv_z_masked) or on one value (wdiv_pos_x, wsqrt_x) do
+// not depend on the row count and are used as they are.  What changes with R <= 256 reliable rows, all within
+// |x - B| < 2^37 of their column's base (a range below 2^38):
+//   - the column sum of x - B stays below 256 * 2^37 = 2^45: exact in fp64, and inside trunc_div_d's |a| < 2^51 with
+//     a divisor R < 2^31 and a quotient below 2^38 < 2^47 (wsad_fast.hpp; recip_lo and tdiv_rel_fix carry no bound
+//     on the row count);
+//   - the sum of the rows' qdev around their truncated mean m: with the exact mean mu, sum (x - m)^2 = sum (x - mu)^2
+//     + R (mu - m)^2 <= R range^2 / 4 + R (Popoviciu) < R 2^74 + R, so sum qdev <= (R 2^74 + R) / 1e6 + R / 2 + R
+//     < 2^62.1 at R = 256: it fits uint64 (and int64) with no carry, and var R <= the sum does too (var_floor_g);
+//   - a reliable row's z: its d^2 <= 1e6 qdev + 5e5 <= 1e6 R (var + 1), and the contract's sqrt of var >= 2 ends at
+//     sd >= 0.999 sqrt(1e6 var) (1414 for var = 2; pinned by the self-test), so |z| <= 1e6 sqrt(R (1 + 1 / var)) /
+//     0.999 + 1 < 1.97e7 at R = 256, var = 2 (var 0 and 1 revert).  z z < 3.9e14 stays in wmul_pos_h's range, z2 z
+//     reaches 7.6e15 (past wmul_t's 2^51 - 2^19) and z2 z2 1.5e17 (int64), s4 n (n + 1) 9.7e15 (past 2^53).
+
+// floor(sv / R) = the population variance (math.cairo:208-222) from the reliable rows' sum of qdev, for
+// 0 <= sv < 2^63 and 1 <= R: a plain unsigned 64-bit division, once per column (no estimate, no correction loop).
+SVOC_HD int64_t var_floor_g(uint64_t sv, int64_t R) { return (int64_t)(sv / (uint64_t)R); }
+
+// The z-score powers for integral |z| <= 2e7 (R <= 256 reliable rows, var >= 2: above): z2 = wsad_mul(z, z) <= 4e8
+// by the half-offset fp64 form (z z <= 4e14 < 2.25e15).  While z2 < 2^25 (|z| < 5.8e6) the fp64 forms of zpow_x hold
+// (|z2 z| < 2^25 5.8e6 < 2^48); past it z3 = I128Div(z2 z + 500000, 1e6) and z4 = I128Div(z2 z2 + 500000, 1e6) in
+// int64 (|z2 z| <= 8e15, z2 z2 <= 1.6e17, both below 2^63; C's division truncates toward zero, as I128Div).
+// |z3| <= 8e9 and z4 <= 1.6e11 are exact doubles.
+SVOC_HD void zpow_g(double zd, double& z2, double& z3, double& z4) {
+  z2 = wmul_pos_h(zd, zd);                                        // wsad_mul(z, z)
+  if (z2 < 33554432.0) {
+    z4 = wmul_pos_h(z2, z2);                                      // wsad_mul(z^2, z^2)
+    z3 = wmul_t(z2, zd);                                          // wsad_mul(z^2, z)
+  } else {
+    const int64_t z2i = (int64_t)z2, zi = (int64_t)zd;
+    z4 = (double)((z2i * z2i + 500000) / 1000000);
+    z3 = (double)((z2i * zi + 500000) / 1000000);
+  }
+}
+
+// skewness = I128Div(s3 n, (n-1)(n-2)); kurtosis = I128Div(I128Div(s4 n (n+1), n-1) - 3 W (n-1)^2, (n-2)(n-3))
+// (math.cairo:336-337, 359-362; the wsad.hpp skew_from_sum / kurt_from_sum) in int64, for 4 <= n <= 256 reliable
+// rows and the sums of zpow_g's powers over them: |s3| <= 256 * 8e9 < 2^41 and 0 <= s4 <= 256 * 1.6e11 < 2^46, so
+// |s3 n| < 2^49 and s4 n (n + 1) < 2^46 * 65792 < 2^63.  Once per column: plain 64-bit divisions.
+SVOC_HD void skew_kurt_g(int64_t s3, int64_t s4, int64_t n, int64_t& sk, int64_t& ku) {
+  sk = (s3 * n) / ((n - 1) * (n - 2));
+  const int64_t t1 = (s4 * n * (n + 1)) / (n - 1);
+  ku = (t1 - 3 * 1000000 * (n - 1) * (n - 1)) / ((n - 2) * (n - 3));
+}
+
 }  // namespace svoc

@@ -12,8 +12,9 @@
 // rel2 from the reliable rows' qr, then variance / sqrt / z-scores / skewness / kurtosis (math.cairo:208-222,
 // 271-292, 320-398).
 //
-// Layout: one workgroup per instance (4 waves), N <= 64, a lane owns one column per slab (the column
-// kernel's NSEG = 1 layout), values taken relative to the column's row-0 value B as int64.  Domain (else
+// Layout: one workgroup per instance (4 waves), N <= 64 (64 < N <= 256: consensus_wsadx_groups.hip, 2 / 4 lanes
+// per column), a lane owns one column per slab (the column kernel's NSEG = 1 layout), values taken relative to the
+// column's row-0 value B as int64.  Domain (else
 // the i128 kernel): |x| < 2^62 and |x - B| < 2^37 (137,438 real units), so that
 //   - the pass-1 keys are exact doubles (the 64-key odd-even merge network of sortnet.hpp on v_min/max_f64,
 //     pruned by dead-code elimination to the median pair),
@@ -362,13 +363,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
 
 using namespace svoc;
 
-// After the column kernel: its flagged instances of whole unconstrained rounds (N <= 64) are taken here where
-// they fit the domain above; `xstats` counts [0] the rounds this kernel committed, [1] the rounds left to the
+extern "C" int svoc_exact_round_wsadx_groups(const ExactParams* p, hipStream_t stream);   // consensus_wsadx_groups.hip
+
+// After the column kernel: its flagged instances of whole unconstrained rounds (N <= 256) are taken here where
+// they fit the domain above -- N <= 64 by the kernel of this file, 64 < N <= 256 by its lane-group form
+// (consensus_wsadx_groups.hip); `xstats` counts [0] the rounds these kernels committed, [1] the rounds left to the
 // i128 kernel (every flagged instance, whatever the round's shape).  -2: nothing launched.
 extern "C" int svoc_exact_round_wsadx(const ExactParams* p, hipStream_t stream) {
   if (p->B <= 0 || !p->fallback || !p->stage) return -2;
-  const bool handle = p->mode == 0 && !p->constrained && !p->legacy && p->N >= 4 && p->N <= 64 && p->win_h == 0 &&
-                      (int64_t)p->N * p->D * (p->val32 ? 4 : 8) < (1ll << 31);
+  const bool whole = p->mode == 0 && !p->constrained && !p->legacy && p->N >= 4 && p->win_h == 0 &&
+                     (int64_t)p->N * p->D * (p->val32 ? 4 : 8) < (1ll << 31);
+  if (whole && p->N > 64 && p->N <= 256) return svoc_exact_round_wsadx_groups(p, stream);
+  const bool handle = whole && p->N <= 64;
   if (!handle && !p->xstats) return -2;
   auto k = p->N == 64 ? (p->val32 ? consensus_wsadx_kernel<true, true> : consensus_wsadx_kernel<false, true>)
                       : (p->val32 ? consensus_wsadx_kernel<true, false> : consensus_wsadx_kernel<false, false>);
