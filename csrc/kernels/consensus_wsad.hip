@@ -250,7 +250,7 @@ SVOC_DEV T group_sum(T v) {
 
 // MODE (launch.hpp ExactParams::mode): 0 whole round; 1 D-sharded first half (c1 + qr partials out);
 // 2 D-sharded second half (c1 and the all-reduced qr in).  Instances it cannot take in mode 1 / 2 go
-// to the i128 kernel's same mode through p.fallback, as in mode 0.
+// to the wide-column / i128 kernels' same mode through p.fallback, as in mode 0 (unconstrained second halves: all).
 // CONS = false: unconstrained rounds (contract.cairo:370-434): signed int64 values, pass-2 consensus = the
 // reliable mean (no second network), reliabilities W - wsad_div(min(ms, sqrt(mean qr)), ms).  Every column is
 // taken relative to its row-0 value B (keys, deviations and z-scores are translation invariant; the two
@@ -325,9 +325,15 @@ void consensus_wsad_kernel(ExactParams p) {
     if (tid == 0) p.fallback[b] = 0;
     return;
   }
+  if constexpr (!CONS && MODE == 2) {
+    // unconstrained, D-sharded second half: no pass 1 here to stage the columns' bases (the commit below adds them
+    // back) or to validate the values against them -- every instance is flagged, for either storage, and the
+    // wide-column kernels (consensus_wsadx.hip, consensus_wsadx_groups.hip) or the i128 kernel take it
+    if (tid == 0) p.fallback[b] = 1;
+    return;
+  }
   if (tid == 0) {
-    // (unconstrained, D-sharded second half over int64 values: no pass 1 here to validate the high words)
-    flag = (!CONS && MODE == 2 && !V32) ? 1 : 0;
+    flag = 0;
     early_st = ST_OK;
     div0 = 0;
   }

@@ -32,7 +32,9 @@
 // The kernel commits only rounds that succeed; anything else (a reliability outside [0, 1], R < 4, a
 // zero-variance column, a value outside the domain) stays flagged and the i128 kernel computes it, status
 // included.  Pass 2 runs in two sweeps (means and sqrt into the staging buffer, checked; then the moments and
-// the outputs), so a round that would revert never touches the outputs.
+// the outputs), so a round that would revert never touches the outputs.  The halves of a D-sharded round
+// (svoc/parallel/dshard.py) are the MODE 1 / 2 instantiations below, with the same rule: a half is done whole or
+// stays flagged.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -100,7 +102,13 @@ SVOC_DEV double dblend(double a, double b, uint32_t m) {   // m ? a : b
 }
 
 // FULLN: N = 64 (every row real, no row masks: the c2 shape); otherwise rows >= N are masked arithmetically
-template <bool V32, bool FULLN>
+// MODE (launch.hpp ExactParams::mode, the halves of a D-sharded round as the i128 kernel splits it): 0 the whole
+// round.  1: pass 1 over this shard's columns -- c1 (staged, written only with the rest) and the per-oracle qr
+// PARTIALS, each below kExactQrPartialMax, status OK; anything else (out of the domain, a carry, a partial at 2^58)
+// stays flagged and writes nothing.  2: the all-reduced qr comes in (each below 2^62, else flagged), then the rank
+// mask, the reliabilities and pass 2 as in a whole round; no pass 1 has validated the values, so pass 2a checks the
+// domain over every row < N itself, before its sqrt and long before the z division of pass 2b.
+template <bool V32, bool FULLN, int MODE = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void consensus_wsadx_kernel(ExactParams p, int handle) {
   constexpr int NT = 256, WAVES = 4, W = WAVES * 64;
   constexpr int ESZ = V32 ? 4 : 8;
@@ -117,6 +125,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
     if (tid == 0 && p.xstats) atomicAdd(&p.xstats[1], 1u);
     return;
   }
+  if constexpr (MODE == 2) {   // a shard's first half failed: the round reverts everywhere, nothing to compute
+    if (p.status[b] != ST_OK) {
+      if (tid == 0) p.fallback[b] = 0;
+      return;
+    }
+  }
   const int N = FULLN ? 64 : p.N, D = p.D;
   const int rowb = D * ESZ;
   const __amdgpu_buffer_rsrc_t rs =
@@ -131,7 +145,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
 
   // ------------------------------------------------------------ pass 1 (contract.cairo:383-395)
   uint64_t acc = 0;   // row `lane`'s qr over the wave's columns
-  for (int s = 0; s < nslab; ++s) {
+  for (int s = 0; s < (MODE == 2 ? 0 : nslab); ++s) {   // (mode 2: no pass 1, the all-reduced qr is read below)
     const int col = s * W + wave * 64 + lane;
     const bool vc = col < D;
     const int vo = (vc ? col : 0) * ESZ;
@@ -164,7 +178,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
       // the sum fits int64; C's division truncates toward zero, as I128Div)
       const int64_t c1a = ((B + (int64_t)k[31]) + (B + (int64_t)k[32])) / 2;
       c1r = c1a - B;
-      if (vc) p.c1[ob + col] = c1a;   // (mode 0: the staged c1, committed where the round succeeds)
+      if constexpr (MODE == 1) {   // (p.c1 is the output itself: staged here, written where the half succeeds)
+        if (vc) {
+          stg[col] = (int32_t)(uint32_t)c1a;
+          stg[D + col] = (int32_t)(uint32_t)((uint64_t)c1a >> 32);
+        }
+      } else {
+        if (vc) p.c1[ob + col] = c1a;   // (mode 0: the staged c1, committed where the round succeeds)
+      }
     }
     // quadratic risk (math.cairo:225-238): qdev(x, c1) of every row, summed over the columns.  (The re-read's
     // offset depends on c1 through an empty asm: otherwise the loads are hoisted above the network and 128 more
@@ -191,16 +212,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
   if (tid < 64) {
     uint64_t v = 0;
     bool o = false;
+    if constexpr (MODE == 2) {   // the all-reduced qr (int64; a negative one reads as >= 2^63)
+      v = tid < N ? (uint64_t)p.qr[(int64_t)b * N + tid] : 0ull;
+    } else {
 #pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-      const uint64_t u = v + qr_part[w][tid];
-      o = o || u < v;
-      v = u;
+      for (int w = 0; w < WAVES; ++w) {
+        const uint64_t u = v + qr_part[w][tid];
+        o = o || u < v;
+        v = u;
+      }
     }
-    if (o || v >= (1ull << 62)) flag = 1;   // (int64 qr, i128 sums below)
+    // (int64 qr, i128 sums below; mode 1: a partial the all-reduce of 32 shards could not hold)
+    if (o || v >= (MODE == 1 ? (uint64_t)kExactQrPartialMax : (1ull << 62))) flag = 1;
     qr_lds[tid] = v;
   }
   __syncthreads();
+  if constexpr (MODE == 1) {   // first half done: c1 and the qr partials out, nothing else
+    if (flag) {
+      if (tid == 0 && p.xstats) atomicAdd(&p.xstats[1], 1u);
+      return;
+    }
+    for (int s = 0; s < nslab; ++s) {   // (each lane reads back the columns it staged)
+      const int col = s * W + wave * 64 + lane;
+      if (col < D)
+        p.c1[ob + col] = (int64_t)(((uint64_t)(uint32_t)stg[D + col] << 32) | (uint32_t)stg[col]);
+    }
+    for (int t = tid; t < N; t += NT) p.qr[(int64_t)b * N + t] = (int64_t)qr_lds[t];
+    if (tid == 0) {
+      p.status[b] = ST_OK;
+      p.fallback[b] = 0;
+      if (p.xstats) atomicAdd(&p.xstats[0], 1u);
+    }
+    return;
+  }
 
   // ------------------------------------------------------------ rank mask (contract.cairo:345-363)
   const int f = p.n_failing;
@@ -219,7 +263,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
     const uint64_t bal = __ballot(rel);
     if (tid == 0) relmask = bal;
   }
-  if (tid == 0) {
+  if (tid == 0 && (MODE != 2 || !flag)) {   // (mode 2: only below 2^62, wsqrt_x's precondition)
     // reliabilities (contract.cairo:365-368) with the wsad.hpp routines; every revert goes to the i128 kernel,
     // which reports the stage-ordered status
     // (the means of the qr are below 2^62: the contract's sqrt in the int64 / fp64-estimate form, wsqrt_x)
@@ -265,10 +309,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
     // fp64: below 64 * 2^37).  The column is read twice (sum, then variance) rather than held: 64 doubles live across
     // the variance loop pushed the kernel past 256 VGPRs (scratch in this loop)
     double Sd = 0.0;
+    double rmax = 0.0;
 #pragma unroll
     for (int i = 0; i < 64; ++i) {
       const int64_t x = xload<V32>(rs, vo, (FULLN || i < N ? i : 0) * rowb1);
-      Sd += dblend((double)(x - B), 0.0, bit_mask(rm1, i));
+      const double rd = (double)(x - B);
+      if constexpr (MODE == 2) rmax = __builtin_fmax(rmax, __builtin_fabs(rd));   // (rows past N read row 0: 0)
+      Sd += dblend(rd, 0.0, bit_mask(rm1, i));
+    }
+    if constexpr (MODE == 2) {
+      // the domain of pass 1, over every row: |B| < 2^61 and |x - B| < 2^37.  Outside it the column's sum and mask
+      // are cleared, so the mean is 0, the variance 0 and its sqrt returns at once; the instance is flagged below
+      const bool od = (uint64_t)(B + (1ll << 61)) >= (1ull << 62) || !(rmax < 137438953472.0);
+      if (od) {
+        Sd = 0.0;
+        rm1 = 0;
+      }
+      bad = bad || (vc && od);
     }
     const double Rd = (double)R, invR = recip_lo(Rd);
     // trunc((R B + S) / R) - B from trunc(S / R) (wsad_fast.hpp tdiv_rel_fix: no R B product)
@@ -301,7 +358,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
   }
   if (bad) flag = 1;
   __syncthreads();
-  if (flag) {   // a zero-variance column (DIV_BY_ZERO): nothing written yet -- the i128 kernel reports it
+  if (flag) {   // a zero-variance column (DIV_BY_ZERO; mode 2: or a value out of the domain): nothing written yet
     if (tid == 0 && p.xstats) atomicAdd(&p.xstats[1], 1u);
     return;
   }
@@ -365,19 +422,28 @@ using namespace svoc;
 
 extern "C" int svoc_exact_round_wsadx_groups(const ExactParams* p, hipStream_t stream);   // consensus_wsadx_groups.hip
 
-// After the column kernel: its flagged instances of whole unconstrained rounds (N <= 256) are taken here where
-// they fit the domain above -- N <= 64 by the kernel of this file, 64 < N <= 256 by its lane-group form
-// (consensus_wsadx_groups.hip); `xstats` counts [0] the rounds these kernels committed, [1] the rounds left to the
-// i128 kernel (every flagged instance, whatever the round's shape).  -2: nothing launched.
+namespace svoc {
+template <int MODE>
+static auto wsadx_kernel_of(const ExactParams& p) {
+  return p.N == 64 ? (p.val32 ? consensus_wsadx_kernel<true, true, MODE> : consensus_wsadx_kernel<false, true, MODE>)
+                   : (p.val32 ? consensus_wsadx_kernel<true, false, MODE> : consensus_wsadx_kernel<false, false, MODE>);
+}
+}  // namespace svoc
+
+// After the column kernel: its flagged instances of unconstrained rounds (N <= 256) -- whole ones and either half of
+// a D-sharded one (ExactParams::mode) -- are taken here where they fit the domain above: N <= 64 by the kernel of
+// this file, 64 < N <= 256 by its lane-group form (consensus_wsadx_groups.hip).  `xstats` counts per launch [0] the
+// instances these kernels took (a whole round committed, or a half done), [1] the ones left to the i128 kernel
+// (every flagged instance, whatever the round's shape).  -2: nothing launched.
 extern "C" int svoc_exact_round_wsadx(const ExactParams* p, hipStream_t stream) {
   if (p->B <= 0 || !p->fallback || !p->stage) return -2;
-  const bool whole = p->mode == 0 && !p->constrained && !p->legacy && p->N >= 4 && p->win_h == 0 &&
+  const bool shape = p->mode >= 0 && p->mode <= 2 && !p->constrained && !p->legacy && p->N >= 4 && p->win_h == 0 &&
                      (int64_t)p->N * p->D * (p->val32 ? 4 : 8) < (1ll << 31);
-  if (whole && p->N > 64 && p->N <= 256) return svoc_exact_round_wsadx_groups(p, stream);
-  const bool handle = whole && p->N <= 64;
+  if (shape && p->N > 64 && p->N <= 256) return svoc_exact_round_wsadx_groups(p, stream);
+  const bool handle = shape && p->N <= 64;
   if (!handle && !p->xstats) return -2;
-  auto k = p->N == 64 ? (p->val32 ? consensus_wsadx_kernel<true, true> : consensus_wsadx_kernel<false, true>)
-                      : (p->val32 ? consensus_wsadx_kernel<true, false> : consensus_wsadx_kernel<false, false>);
+  // (a shape not taken here runs the whole-round kernel's counting branch only)
+  auto k = !handle || p->mode == 0 ? wsadx_kernel_of<0>(*p) : p->mode == 1 ? wsadx_kernel_of<1>(*p) : wsadx_kernel_of<2>(*p);
   hipLaunchKernelGGL(k, dim3(p->B), dim3(256), 0, stream, *p, handle ? 1 : 0);
   return (int)hipGetLastError();
 }

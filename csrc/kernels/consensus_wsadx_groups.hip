@@ -181,7 +181,10 @@ SVOC_DEV int64_t xload(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
 }
 
 // FULLN: N = 64 NSEG (every row real, no row masks: the c3 shape); otherwise the rows >= N are masked arithmetically
-template <bool V32, int NSEG, bool FULLN>
+// MODE: 0 the whole round; 1 / 2 the halves of a D-sharded round, as in the N <= 64 kernel (consensus_wsadx.hip):
+// 1 writes c1 and the qr partials (each below kExactQrPartialMax) or nothing; 2 reads the all-reduced qr (each
+// below 2^62) and runs the rank mask, the reliabilities and pass 2, pass 2a checking the domain over every row.
+template <bool V32, int NSEG, bool FULLN, int MODE = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void consensus_wsadx_group_kernel(ExactParams p) {
   constexpr int NT = 256, WAVES = 4, P = 64 / NSEG, W = WAVES * P, NPAD = 64 * NSEG, KEEP = NSEG;
   constexpr int ESZ = V32 ? 4 : 8;
@@ -195,6 +198,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
   if (!p.fallback[b]) return;   // (the column kernel took it, or the instance is inactive)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int seg = lane / P, pw = lane % P;
+  if constexpr (MODE == 2) {   // a shard's first half failed: the round reverts everywhere, nothing to compute
+    if (p.status[b] != ST_OK) {
+      if (tid == 0) p.fallback[b] = 0;
+      return;
+    }
+  }
   const int N = FULLN ? NPAD : p.N, D = p.D;
   const int rowb = D * ESZ;
   const __amdgpu_buffer_rsrc_t rs =
@@ -217,7 +226,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
   uint64_t acc[KEEP];   // rows KEEP lane .. KEEP lane + KEEP - 1: their qr over the wave's columns
 #pragma unroll
   for (int j = 0; j < KEEP; ++j) acc[j] = 0;
-  for (int s = 0; s < nslab; ++s) {
+  for (int s = 0; s < (MODE == 2 ? 0 : nslab); ++s) {   // (mode 2: no pass 1, the all-reduced qr is read below)
     const int col = s * W + wave * P + pw;
     const bool vc = col < D;
     const int vo = (vc ? col : 0) * ESZ;
@@ -252,7 +261,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
       // be anything: the conversions saturate, and the instance is flagged.)
       const int64_t c1a = ((B + (int64_t)klo) + (B + (int64_t)khi)) / 2;
       c1r = c1a - B;
-      if (vc && first) p.c1[ob + col] = c1a;   // (the staged c1, committed where the round succeeds)
+      if constexpr (MODE == 1) {   // (p.c1 is the output itself: staged here, written where the half succeeds)
+        if (vc && first) {
+          stg[col] = (int32_t)(uint32_t)c1a;
+          stg[D + col] = (int32_t)(uint32_t)((uint64_t)c1a >> 32);
+        }
+      } else {
+        if (vc && first) p.c1[ob + col] = c1a;   // (the staged c1, committed where the round succeeds)
+      }
     }
     // quadratic risk (math.cairo:225-238): qdev(x, c1) of every row, summed over the columns.  (The re-read's
     // offset depends on c1 through an empty asm: the loads stay below the network.)
@@ -284,16 +300,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
   if (tid < NPAD) {
     uint64_t v = 0;
     bool o = false;
+    if constexpr (MODE == 2) {   // the all-reduced qr (int64; a negative one reads as >= 2^63)
+      v = tid < N ? (uint64_t)p.qr[(int64_t)b * N + tid] : 0ull;
+    } else {
 #pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-      const uint64_t u = v + qr_part[w][tid];
-      o = o || u < v;
-      v = u;
+      for (int w = 0; w < WAVES; ++w) {
+        const uint64_t u = v + qr_part[w][tid];
+        o = o || u < v;
+        v = u;
+      }
     }
-    if (tid < N && (o || v >= (1ull << 62))) flag = 1;   // (int64 qr, i128 sums below)
+    // (int64 qr, i128 sums below; mode 1: a partial the all-reduce of 32 shards could not hold)
+    if (tid < N && (o || v >= (MODE == 1 ? (uint64_t)kExactQrPartialMax : (1ull << 62)))) flag = 1;
     qr_lds[tid] = v;
   }
   __syncthreads();
+  if constexpr (MODE == 1) {   // first half done: c1 and the qr partials out, nothing else
+    if (flag) {
+      if (tid == 0 && p.xstats) atomicAdd(&p.xstats[1], 1u);
+      return;
+    }
+    for (int s = 0; s < nslab; ++s) {   // (the group's first lane reads back the columns it staged)
+      const int col = s * W + wave * P + pw;
+      if (col < D && first)
+        p.c1[ob + col] = (int64_t)(((uint64_t)(uint32_t)stg[D + col] << 32) | (uint32_t)stg[col]);
+    }
+    for (int t = tid; t < N; t += NT) p.qr[(int64_t)b * N + t] = (int64_t)qr_lds[t];
+    if (tid == 0) {
+      p.status[b] = ST_OK;
+      p.fallback[b] = 0;
+      if (p.xstats) atomicAdd(&p.xstats[0], 1u);
+    }
+    return;
+  }
 
   // ------------------------------------------------------------ rank mask (contract.cairo:345-363)
   const int f = p.n_failing;
@@ -358,13 +397,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
     // the reliable mean (math.cairo:240-254): I128Div of the absolute sum by R.  The relative sum is exact in
     // fp64: below 64 * 2^37 in the lane, below 2^45 over the group.  The column is read twice (sum, then variance).
     double Sl = 0.0;
+    double rmax = 0.0;
 #pragma unroll
     for (int i = 0; i < 64; ++i) {
       const uint32_t mr = FULLN ? 0xffffffffu : lt_mask(i, n1);
       const int64_t x = xload<V32>(rs, vo + (so1 & (int)mr), i * rowb1);
-      Sl += dblend((double)(x - B), 0.0, bit_mask(rm1, i));
+      const double rd = (double)(x - B);
+      if constexpr (MODE == 2) rmax = __builtin_fmax(rmax, __builtin_fabs(rd));   // (a masked row reads a real one)
+      Sl += dblend(rd, 0.0, bit_mask(rm1, i));
     }
-    const double Sd = group_sum_f64<NSEG>(Sl);
+    double Sd = group_sum_f64<NSEG>(Sl);
+    if constexpr (MODE == 2) {
+      // the domain of pass 1, over every row of the group's lanes: |B| < 2^61 and |x - B| < 2^37.  Outside it the
+      // column's sum and mask are cleared, so the mean is 0, the variance 0 and its sqrt returns at once; the
+      // instance is flagged below
+      if constexpr (NSEG == 4) rmax = __builtin_fmax(rmax, xor_lane_f64<16>(rmax));
+      rmax = __builtin_fmax(rmax, xor_lane_f64<32>(rmax));
+      const bool od = (uint64_t)(B + (1ll << 61)) >= (1ull << 62) || !(rmax < 137438953472.0);
+      if (od) {
+        Sd = 0.0;
+        rm1 = 0;
+      }
+      bad = bad || (vc && od);
+    }
     const double Rd = (double)R, invR = recip_lo(Rd);
     // trunc((R B + S) / R) - B from trunc(S / R) (wsad_fast.hpp tdiv_rel_fix; |S| < 2^45 < 2^51, R <= 256)
     const double qd = trunc_div_d(Sd, Rd, invR);
@@ -397,7 +452,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
   }
   if (bad) flag = 1;
   __syncthreads();
-  if (flag) {   // a zero-variance column (DIV_BY_ZERO): nothing written yet -- the i128 kernel reports it
+  if (flag) {   // a zero-variance column (DIV_BY_ZERO; mode 2: or a value out of the domain): nothing written yet
     if (tid == 0 && p.xstats) atomicAdd(&p.xstats[1], 1u);
     return;
   }
@@ -459,18 +514,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
 
 using namespace svoc;
 
-// The flagged instances of whole unconstrained rounds with 64 < N <= 256 (the caller, svoc_exact_round_wsadx,
-// has checked the round's shape): `xstats` [0] += rounds committed here, [1] += rounds left to the i128 kernel.
-extern "C" int svoc_exact_round_wsadx_groups(const ExactParams* p, hipStream_t stream) {
-  if (p->N <= 64 || p->N > 256) return -1;
+namespace svoc {
+template <int MODE>
+static auto wsadx_group_kernel_of(const ExactParams& p) {
   void (*k)(ExactParams);
-  if (p->N <= 128) {
-    k = p->N == 128 ? (p->val32 ? wxg::consensus_wsadx_group_kernel<true, 2, true> : wxg::consensus_wsadx_group_kernel<false, 2, true>)
-                    : (p->val32 ? wxg::consensus_wsadx_group_kernel<true, 2, false> : wxg::consensus_wsadx_group_kernel<false, 2, false>);
+  if (p.N <= 128) {
+    k = p.N == 128 ? (p.val32 ? wxg::consensus_wsadx_group_kernel<true, 2, true, MODE> : wxg::consensus_wsadx_group_kernel<false, 2, true, MODE>)
+                   : (p.val32 ? wxg::consensus_wsadx_group_kernel<true, 2, false, MODE> : wxg::consensus_wsadx_group_kernel<false, 2, false, MODE>);
   } else {
-    k = p->N == 256 ? (p->val32 ? wxg::consensus_wsadx_group_kernel<true, 4, true> : wxg::consensus_wsadx_group_kernel<false, 4, true>)
-                    : (p->val32 ? wxg::consensus_wsadx_group_kernel<true, 4, false> : wxg::consensus_wsadx_group_kernel<false, 4, false>);
+    k = p.N == 256 ? (p.val32 ? wxg::consensus_wsadx_group_kernel<true, 4, true, MODE> : wxg::consensus_wsadx_group_kernel<false, 4, true, MODE>)
+                   : (p.val32 ? wxg::consensus_wsadx_group_kernel<true, 4, false, MODE> : wxg::consensus_wsadx_group_kernel<false, 4, false, MODE>);
   }
+  return k;
+}
+}  // namespace svoc
+
+// The flagged instances of unconstrained rounds with 64 < N <= 256, whole or either half of a D-sharded one (the
+// caller, svoc_exact_round_wsadx, has checked the round's shape): `xstats` [0] += instances taken here,
+// [1] += instances left to the i128 kernel.
+extern "C" int svoc_exact_round_wsadx_groups(const ExactParams* p, hipStream_t stream) {
+  if (p->N <= 64 || p->N > 256 || p->mode < 0 || p->mode > 2) return -1;
+  auto k = p->mode == 0 ? wsadx_group_kernel_of<0>(*p) : p->mode == 1 ? wsadx_group_kernel_of<1>(*p) : wsadx_group_kernel_of<2>(*p);
   hipLaunchKernelGGL(k, dim3(p->B), dim3(256), 0, stream, *p);
   return (int)hipGetLastError();
 }

@@ -129,8 +129,9 @@ def run_round_sharded(engine, d_global: int, group=None, world: int = 1, defer: 
         head = (e.values, e._active, e.cfg.n_failing_oracles, e.cfg.constrained, e.cfg.max_spread_wsad, sh.c1)
 
         def half(mode):
+            # the routing counters (engine.exact_routing) on the second half only: a sharded round counts once
             e._ops.exact_round(*head, sh.consensus, sh.skew, sh.kurt, sh.rel, sh.qr, sh.reliable, e.status, lg,
-                               mode, d_global)
+                               mode, d_global, stats=e._xstats if mode == 2 else None)
     # pass 1: local c1 + qr partials into the shadow qr (the committed qr stays intact); status = this
     # shard's pass-1 verdict (exact: a partial past 2^58 fails the round)
     half(1)
