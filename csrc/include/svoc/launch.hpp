@@ -123,8 +123,8 @@ struct ExactParams {
   int mode;
   int rel_dim;
   int win_h;                // the column kernel's window half-width (exact_win_h; the stage holds 4 + 2 win_h rows)
-  // [2] or null, per launch: += instances the wide-column unconstrained kernels took (consensus_wsadx.hip,
-  // consensus_wsadx_groups.hip: a whole round committed, or a D-sharded half done), += instances left to the i128 kernel
+  // [2] or null, per launch: += instances the wide-column unconstrained kernel took (consensus_wsadx.hip: a whole
+  // round committed, or a D-sharded half done), += instances left to the i128 kernel
   unsigned int* xstats;
   // verdict rounds (svoc_exact_verdict): uint32 [3] or null: [0] += rounds the verdict form of the column kernel
   // judged, [1] += rounds handed to the full-round path; [2] belongs to the engine (final rounds of a

@@ -115,7 +115,7 @@ SVOC_HD void skew_kurt_x(double s3, double s4, double Rd, double& sk, double& ku
   ku = trunc_div_d(t1 - t2, k4d, ik4);
 }
 
-// ---- Up to 256 reliable rows (consensus_wsadx_groups.hip: lane groups of 2 / 4, 64 < N <= 256) ---------------------
+// ---- Up to 256 reliable rows (consensus_wsadx.hip, NSEG > 1: lane groups of 2 / 4, 64 < N <= 256) -----------------
 // The routines above that work on one row (qdev_dd, wdiv_z, wdiv_z_masked) or on one value (wdiv_pos_x, wsqrt_x) do
 // not depend on the row count and are used as they are.  What changes with R <= 256 reliable rows, all within
 // |x - B| < 2^37 of their column's base (a range below 2^38):

@@ -453,7 +453,7 @@ extern "C" int svoc_exact_round(const ExactParams* p, hipStream_t stream) {
     if (rc != -2) {
       if (rc != 0 || p->skip_fallback) return rc;
       // flagged unconstrained rounds over wide columns: the int64 column kernel first (it clears the flags of
-      // the rounds it commits; consensus_wsadx.hip), the i128 kernel for the rest
+      // the rounds it commits; consensus_wsadx.hip, N <= 256), the i128 kernel for the rest
       const int rx = svoc_exact_round_wsadx(p, stream);
       if (rx != 0 && rx != -2) return rx;
       ExactParams q = *p;

@@ -328,7 +328,7 @@ void consensus_wsad_kernel(ExactParams p) {
   if constexpr (!CONS && MODE == 2) {
     // unconstrained, D-sharded second half: no pass 1 here to stage the columns' bases (the commit below adds them
     // back) or to validate the values against them -- every instance is flagged, for either storage, and the
-    // wide-column kernels (consensus_wsadx.hip, consensus_wsadx_groups.hip) or the i128 kernel take it
+    // wide-column kernel (consensus_wsadx.hip) or the i128 kernel takes it
     if (tid == 0) p.fallback[b] = 1;
     return;
   }

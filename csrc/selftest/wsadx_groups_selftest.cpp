@@ -1,6 +1,6 @@
 // Host self-test of the R <= 256 arithmetic of the wide-column exact kernel's lane-group form
 // (svoc/wsad_wide.hpp: var_floor_g, zpow_g, skew_kurt_g, and the row-count-independent routines at the values
-// 256 rows reach; consensus_wsadx_groups.hip calls exactly these) against the i128 routines of svoc/wsad.hpp:
+// 256 rows reach; consensus_wsadx.hip calls exactly these for NSEG > 1) against the i128 routines of svoc/wsad.hpp:
 // exact integer comparisons, inside each stated precondition and at its edges.  Stand-alone (its own main), built
 // by tests/test_wsadx_groups_host.py with the address and undefined-behaviour sanitizers.
 #include <algorithm>

@@ -547,7 +547,7 @@ class ConsensusEngine:
     def exact_routing(self) -> Dict[str, int]:
         """Exact engine on the GPU: how the rounds so far were computed -- ``processed`` rounds, of which
         ``wide_column`` committed by the int64 wide-column kernel (unconstrained columns spread past 2^30 wsad,
-        up to 256 oracles: consensus_wsadx.hip, consensus_wsadx_groups.hip) and ``i128`` handed to the i128 kernel (out of every column kernel's domain, or
+        up to 256 oracles: consensus_wsadx.hip) and ``i128`` handed to the i128 kernel (out of every column kernel's domain, or
         reverting where the wide-column kernel cannot name the status); the rest ran on the column kernel."""
         self.pipeline_join()
         processed = int(self.metrics_fx[2].item())

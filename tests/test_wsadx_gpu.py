@@ -7,48 +7,12 @@ signed_decimal.cairo:52-116, math.cairo:113-398), and every round it cannot take
 must still come out right through the i128 kernel.  The routing counters (engine.exact_routing) say which kernel
 ran.
 """
-import os
-
 import pytest
 import torch
 
-from helpers import alloc_exact_out, beta_oracles
-from svoc import ops as svops
+from wsadx_cases import DEV, DIV_BY_ZERO, MS, OUTS, UNIT, _honest, _prices, _run
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-OUTS = ("c1", "consensus", "skew", "kurt", "rel", "qr", "reliable", "status")
-MS = 10 ** 12   # max_spread (wsad): 1e6 real units
-
-
-def _run(values, f, env=None, ms=MS):
-    B, N, D = values.shape
-    o = alloc_exact_out(B, N, D, values.device)
-    stats = torch.zeros(2, dtype=torch.int32, device=values.device) if values.is_cuda else None
-    old = {k: os.environ.get(k) for k in ("SVOC_EXACT_I128", "SVOC_EXACT_WSAD_ONLY", "SVOC_EXACT_WSAD_MIN_D")}
-    try:
-        for k in old:
-            os.environ.pop(k, None)
-        os.environ.update(env or {})
-        svops.ops().exact_round(values, None, f, False, ms, o["c1"], o["consensus"], o["skew"], o["kurt"], o["rel"],
-                                o["qr"], o["reliable"], o["status"], False, stats=stats)
-        if values.is_cuda:
-            torch.cuda.synchronize()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    out = {k: v.cpu() for k, v in o.items()}
-    out["stats"] = stats.cpu().tolist() if stats is not None else None
-    return out
-
-
-def _prices(B, N, D, f, seed, centre=60_000.0, spread=20_000.0):
-    """Beta(20,20) honest / U(0,1) failing draws mapped onto centre +- spread real units (int64 wsad)."""
-    x, _ = beta_oracles(B, N, D, f, seed=seed, dtype=torch.float64)
-    return (((x[:, :, :D] - 0.5) * (2.0 * spread) + centre) * 1e6).round().to(torch.int64).contiguous()
 
 
 def _check(v, f, expect_wide, ms=MS):
@@ -143,16 +107,6 @@ def test_engine_reports_routing():
 # data never produces.  Every test asserts, from the CPU engine's result, the condition that makes it reach the
 # branch it is about, then compares the wide-column kernel, the i128 kernel and the CPU engine bit for bit.
 # ---------------------------------------------------------------------------------------------------------
-UNIT = 10 ** 6            # one real unit in wsad
-DIV_BY_ZERO = 4           # svoc/status.py
-
-
-def _honest(B, N, D, seed, centre=1000 * UNIT, jitter=20_000):
-    """Honest oracles: every value within +-jitter wsad of the centre (int64 wsad)."""
-    g = torch.Generator().manual_seed(seed)
-    return centre + torch.randint(-jitter, jitter + 1, (B, N, D), generator=g, dtype=torch.int64)
-
-
 def _column_z(v, cpu, b, c):
     """(exact |x - mean| per row, an upper bound of the reliable rows' sd) of column c of instance b, in wsad:
     the variance is floor(mean of floor((d^2 + 500000) / 1e6)) <= mean(d^2) / 1e6 + 1 and the contract's Newton
@@ -237,6 +191,26 @@ def test_qr_sum_hand_offs(D, lo, hi, wide):
         trunc = (qr + (1 << 63)) % (1 << 64) - (1 << 63)
         assert int(cpu["qr"][b, rows[b]]) == trunc
     assert got["stats"] == ([B, 0] if wide else [0, B])
+
+
+def test_many_qr_sums_past_2_62_hand_off():
+    """N = 64: rows 0 and 1 equal, half of the others 2^37 - 1 above row 0 and half below it in all 640 columns.
+    c1 is row 0, each far row's qr sum is 2^63.39 (no carry out of uint64) and the mean of the 64 sums 2^63.35 --
+    negative as int64, outside the Newton sqrt's domain: the instance is flagged before the reliabilities are
+    computed and the i128 kernel takes it."""
+    B, N, D, f = 2, 64, 640, 8
+    v = _honest(B, N, D, seed=350)
+    v[:, 1, :] = v[:, 0, :]
+    v[:, 2::2, :] = v[:, :1, :] + (1 << 37) - 1
+    v[:, 3::2, :] = v[:, :1, :] - (1 << 37) + 1
+    cpu = _run(v, f)
+    for b in range(B):
+        assert torch.equal(cpu["c1"][b], v[b, 0])
+        qr = [sum(((int(x) - int(c)) ** 2 + 500000) // UNIT for x, c in zip(v[b, r], cpu["c1"][b])) for r in range(N)]
+        assert all((1 << 62) <= q < (1 << 64) for q in qr[2:]), [q / 2 ** 62 for q in qr[2:]]
+        assert (1 << 63) <= sum(qr) // N < (1 << 64), sum(qr) / N / 2 ** 63
+    got = _check(v, f, expect_wide=0)
+    assert got["stats"] == [0, B]
 
 
 @pytest.mark.parametrize("amp,var", [(1000, 1), (1500, 2)])

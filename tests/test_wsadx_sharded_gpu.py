@@ -1,6 +1,5 @@
-"""D-sharded exact unconstrained rounds on the int64 wide-column kernels (csrc/kernels/consensus_wsadx.hip for N <= 64,
-consensus_wsadx_groups.hip for 64 < N <= 256): mode 1 (this shard's c1 and qr partials) and mode 2 (pass 2 from the
-all-reduced qr).
+"""D-sharded exact unconstrained rounds on the int64 wide-column kernel (csrc/kernels/consensus_wsadx.hip, N <= 256):
+mode 1 (this shard's c1 and qr partials) and mode 2 (pass 2 from the all-reduced qr).
 
 Every case compares three results bit for bit on all eight outputs -- the default path, the i128 kernel
 (SVOC_EXACT_I128=1) and the CPU engine -- over outputs prefilled with a pattern (an unwanted write shows), and asserts
@@ -15,60 +14,21 @@ import tempfile
 import pytest
 import torch
 
-from helpers import alloc_exact_out, beta_oracles
-from svoc import ops as svops
+from wsadx_cases import DEV, DIV_BY_ZERO, OK, OUTS, OVERFLOW, PATTERN, UNIT, _prices, _run
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-OUTS = ("c1", "consensus", "skew", "kurt", "rel", "qr", "reliable", "status")
-MS = 10 ** 12             # max_spread (wsad): 1e6 real units
-UNIT = 10 ** 6            # one real unit in wsad
-OK, DIV_BY_ZERO, OVERFLOW = 0, 4, 7      # svoc/status.py
-PATTERN = {"c1": -101, "consensus": -102, "skew": -103, "kurt": -104, "rel": -105, "qr": -106, "reliable": 7,
-           "status": -1}
 # (N, D, f) and where D is cut: the first shard ends one or two columns past a slab edge
 SHAPES = [(7, 300, 1), (64, 520, 8), (100, 140, 12), (128, 260, 16), (200, 70, 24), (256, 130, 32)]
 CUT = {7: 257, 64: 300, 100: 129, 128: 129, 200: 65, 256: 66}
 
 
-def _run(values, f, mode, rel_dim=0, inp=None, env=None, ms=MS, active=None):
-    """One launch of exact_round in `mode` over outputs prefilled with PATTERN; `inp`: the inputs of the half
-    (mode 2: c1, qr, status) copied over the pattern first."""
-    B, N, D = values.shape
-    o = alloc_exact_out(B, N, D, values.device)
-    for k, p in PATTERN.items():
-        o[k].fill_(p)
-    for k, t in (inp or {}).items():
-        o[k].copy_(t.to(values.device))
-    stats = torch.zeros(2, dtype=torch.int32, device=values.device) if values.is_cuda else None
-    if active is not None:
-        active = active.to(values.device)
-    old = {k: os.environ.get(k) for k in ("SVOC_EXACT_I128", "SVOC_EXACT_WSAD_ONLY", "SVOC_EXACT_WSAD_MIN_D")}
-    try:
-        for k in old:
-            os.environ.pop(k, None)
-        os.environ.update(env or {})
-        svops.ops().exact_round(values, active, f, False, ms, o["c1"], o["consensus"], o["skew"], o["kurt"], o["rel"],
-                                o["qr"], o["reliable"], o["status"], False, mode, rel_dim, stats=stats)
-        if values.is_cuda:
-            torch.cuda.synchronize()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    out = {k: v.cpu() for k, v in o.items()}
-    out["stats"] = stats.cpu().tolist() if stats is not None else None
-    return out
-
-
 def _check(v, f, mode, expect, rel_dim=0, inp=None, storage=torch.int64, active=None):
     """The three results, bit for bit; `expect` = [wide-column halves, i128 halves] of the default path.  Returns
     (default path, CPU engine)."""
-    cpu = _run(v, f, mode, rel_dim, inp, active=active)
-    i128 = _run(v.to(DEV, storage), f, mode, rel_dim, inp, {"SVOC_EXACT_I128": "1"}, active=active)
-    got = _run(v.to(DEV, storage), f, mode, rel_dim, inp, {"SVOC_EXACT_WSAD_MIN_D": "1"}, active=active)
+    kw = dict(mode=mode, rel_dim=rel_dim, inp=inp, prefill=True, active=active)     # (an unwanted write shows)
+    cpu = _run(v, f, **kw)
+    i128 = _run(v.to(DEV, storage), f, {"SVOC_EXACT_I128": "1"}, **kw)
+    got = _run(v.to(DEV, storage), f, {"SVOC_EXACT_WSAD_MIN_D": "1"}, **kw)
     print(f"mode {mode} N {v.shape[1]} D {v.shape[2]} {storage}: stats {got['stats']} (expected {list(expect)}), "
           f"status {cpu['status'].tolist()}")
     for k in OUTS:
@@ -77,12 +37,6 @@ def _check(v, f, mode, expect, rel_dim=0, inp=None, storage=torch.int64, active=
     assert got["stats"] == list(expect), got["stats"]
     assert i128["stats"] == [0, 0], i128["stats"]       # (the forced i128 run has no column kernel to count)
     return got, cpu
-
-
-def _prices(B, N, D, f, seed, centre=60_000.0, spread=20_000.0):
-    """Beta(20,20) honest / U(0,1) failing draws mapped onto centre +- spread real units (int64 wsad)."""
-    x, _ = beta_oracles(B, N, D, f, seed=seed, dtype=torch.float64)
-    return (((x[:, :, :D] - 0.5) * (2.0 * spread) + centre) * 1e6).round().to(torch.int64).contiguous()
 
 
 def _shards(v, cut):
@@ -114,7 +68,7 @@ def _sharded_round(v, f, cut, storage=torch.int64, expect1=None, expect2=None):
     qr = first[0]["qr"] + first[1]["qr"]
     second = [_check(s, f, 2, expect2, D, {"c1": h["c1"], "qr": qr, "status": h["status"]}, storage=storage)[0]
               for s, h in zip(parts, first)]
-    whole = _run(v, f, 0)                                     # the CPU engine, unsharded
+    whole = _run(v, f, prefill=True)                          # the CPU engine, unsharded
     assert (whole["status"] == OK).all()
     for k in ("c1", "consensus", "skew", "kurt"):
         assert torch.equal(torch.cat([second[0][k], second[1][k]], 1), whole[k]), k
