@@ -256,7 +256,9 @@ at::Tensor attention_hip(const at::Tensor& qkv, const c10::optional<at::Tensor>&
   return out;
 }
 
-// packed (unpadded) tokens: qkv [T, 3*H*DH], sequence b = rows [cu[b], cu[b+1])
+// packed (unpadded) tokens: qkv [T, 3*H*DH], sequence b = rows [cu[b], cu[b+1]).  Contract of the HIP
+// path: every segment length <= max_len rounded up to 32, or the output rows of the longer segment are
+// left unwritten (cu_seqlens lives on the device: checking it here would cost a sync).
 at::Tensor attention_varlen_ref(const at::Tensor& qkv, const at::Tensor& cu, int64_t max_len, int64_t heads) {
   (void)max_len;
   const int64_t T = qkv.size(0), HD = qkv.size(1) / 3, DH = HD / heads;

@@ -3,9 +3,31 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import encoder_cases as ec
 from svoc import ops as svops
 
 pytestmark = pytest.mark.gpu
+
+
+def _ln_bound_holds(out, x, y, w, b):
+    """out against the fp64 LayerNorm of x + y within encoder_cases' bound: 0.5 ulp_bf16(ref64) + s (bf16)."""
+    ref, s = ec.ln_ref64(x.double().cpu() + y.double().cpu(), w.cpu(), b.cpu())
+    r = ec.ln_ratio(out.cpu(), ref, s, "bf16")
+    assert r <= 1, r
+
+
+def _attn_bound_holds(out, qkv, mask, heads, storage):
+    """Padded attention against ref64 on the op's own inputs within encoder_cases.attn_ratio's bound."""
+    qkv, mask = qkv.cpu(), None if mask is None else mask.cpu()
+    ref, A = ec.attn_ref(qkv, heads, mask)
+    r = ec.attn_ratio(out.cpu(), ref, A, storage, ec.attn_ref(qkv, heads, mask, torch.float32)[0])
+    assert r <= 1, r
+
+
+def _varlen_bound_holds(out, qkv, lens, heads, storage):
+    ref, A = ec.varlen_ref(qkv.cpu(), lens, heads)
+    r = ec.attn_ratio(out.cpu(), ref, A, storage, ec.varlen_ref(qkv.cpu(), lens, heads, torch.float32)[0])
+    assert r <= 1, r
 
 
 @pytest.mark.parametrize("rows,H", [(1, 768), (1023, 768), (257, 256), (64, 1024), (5, 512)])
@@ -19,8 +41,8 @@ def test_add_layernorm_bf16(rows, H):
     ref = F.layer_norm(x.float() + y.float(), (H,), w.float(), b.float(), 1e-5)
     assert out.dtype == torch.bfloat16 and out.shape == x.shape
     torch.testing.assert_close(out.float(), ref, rtol=1e-2, atol=2e-2)
-    # bf16 rounding of the output is the only error source: compare against the rounded reference
-    assert (out.float() - ref.to(torch.bfloat16).float()).abs().max().item() <= 0.0625
+    # bf16 rounding of the output is the only error source beyond the fp32 arithmetic
+    _ln_bound_holds(out, x, y, w, b)
 
 
 @pytest.mark.parametrize("H", [768, 256])
@@ -32,8 +54,7 @@ def test_add_layernorm_broadcast_row(H):
     w = (1 + 0.1 * torch.randn(H, device="cuda", generator=g)).to(torch.bfloat16)
     b = (0.1 * torch.randn(H, device="cuda", generator=g)).to(torch.bfloat16)
     out = svops.ops().add_layernorm(x, y, w, b, 1e-5)
-    ref = F.layer_norm(x.float() + y.float()[None], (H,), w.float(), b.float(), 1e-5)
-    assert (out.float() - ref.to(torch.bfloat16).float()).abs().max().item() <= 0.0625
+    _ln_bound_holds(out, x, y[None], w, b)
 
 
 def test_add_layernorm_3d_and_fallback_width():
@@ -46,17 +67,6 @@ def test_add_layernorm_3d_and_fallback_width():
                                rtol=2e-2, atol=3e-2)
 
 
-def _attn_ref(qkv, mask, heads):
-    B, S, H3 = qkv.shape
-    HD = H3 // 3
-    DH = HD // heads
-    t = qkv.float().view(B, S, 3, heads, DH).permute(2, 0, 3, 1, 4)
-    s = t[0] @ t[1].transpose(-1, -2) / DH ** 0.5
-    if mask is not None:
-        s = s.masked_fill(~mask.bool()[:, None, None, :], float("-inf"))
-    return (torch.softmax(s, -1) @ t[2]).transpose(1, 2).reshape(B, S, HD)
-
-
 @pytest.mark.parametrize("S", [32, 64, 96, 128])
 def test_attention_qkv_mfma(S):
     B, heads = 5, 12
@@ -65,11 +75,9 @@ def test_attention_qkv_mfma(S):
     lens = torch.randint(1, S + 1, (B,), device="cuda", generator=g)
     mask = (torch.arange(S, device="cuda")[None] < lens[:, None]).to(torch.uint8)
     out = svops.ops().attention_qkv(qkv, mask, heads)
-    ref = _attn_ref(qkv, mask, heads)
     assert out.shape == (B, S, heads * 64) and out.dtype == torch.bfloat16
-    torch.testing.assert_close(out.float(), ref, rtol=3e-2, atol=3e-2)
-    out2 = svops.ops().attention_qkv(qkv, None, heads)
-    torch.testing.assert_close(out2.float(), _attn_ref(qkv, None, heads), rtol=3e-2, atol=3e-2)
+    _attn_bound_holds(out, qkv, mask, heads, "bf16")
+    _attn_bound_holds(svops.ops().attention_qkv(qkv, None, heads), qkv, None, heads, "bf16")
 
 
 def test_encoder_fused_matches_cpu_fp32():
@@ -133,8 +141,8 @@ def test_attention_varlen_mfma():
     g = torch.Generator(device="cuda").manual_seed(1)
     qkv = torch.randn(T, 3 * heads * 64, device="cuda", generator=g).to(torch.bfloat16)
     out = svops.ops().attention_varlen(qkv, cu, max(lens), heads)
-    ref = svops.ops().attention_varlen(qkv.cpu().float(), cu.cpu(), max(lens), heads)   # CPU reference path
-    torch.testing.assert_close(out.float().cpu(), ref.float(), rtol=3e-2, atol=3e-2)
+    assert out.shape == (T, heads * 64) and out.dtype == torch.bfloat16
+    _varlen_bound_holds(out, qkv, lens, heads, "bf16")           # the independent fp64 reference
 
 
 def test_encoder_packed_equals_padded():
@@ -251,8 +259,10 @@ def test_attention_qkv_f32_mfma(S):
     out = svops.ops().attention_qkv(qkv, mask, heads)
     assert out.dtype == torch.float32 and out.shape == (B, S, heads * 64)
     torch.testing.assert_close(out.double(), _attn_ref64(qkv, mask, heads), rtol=0, atol=2e-5)
+    _attn_bound_holds(out, qkv, mask, heads, "fp32")
     out2 = svops.ops().attention_qkv(qkv, None, heads)
     torch.testing.assert_close(out2.double(), _attn_ref64(qkv, None, heads), rtol=0, atol=2e-5)
+    _attn_bound_holds(out2, qkv, None, heads, "fp32")
 
 
 def test_attention_varlen_f32_mfma():
@@ -262,7 +272,9 @@ def test_attention_varlen_f32_mfma():
     T = int(cu[-1])
     qkv = torch.randn(T, 3 * heads * 64, device="cuda", generator=torch.Generator(device="cuda").manual_seed(3))
     out = svops.ops().attention_varlen(qkv, cu, max(lens), heads)
-    ref = svops.ops().attention_varlen(qkv.cpu().double(), cu.cpu(), max(lens), heads)
+    _varlen_bound_holds(out, qkv, lens, heads, "fp32")           # the independent fp64 reference
+    torch.testing.assert_close(out.double().cpu(), ec.varlen_ref(qkv.cpu(), lens, heads)[0], rtol=0, atol=2e-5)
+    ref = svops.ops().attention_varlen(qkv.cpu().double(), cu.cpu(), max(lens), heads)   # and the CPU op
     torch.testing.assert_close(out.double().cpu(), ref, rtol=0, atol=2e-5)
 
 
