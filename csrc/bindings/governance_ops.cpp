@@ -1,4 +1,5 @@
-// torch.ops.svoc.governance: batched update_proposition / vote_for_a_proposition; find_address: batched lookup.
+// torch.ops.svoc.governance: batched update_proposition / vote_for_a_proposition (governance_track: with the
+// per-oracle track record); find_address: batched lookup.
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
@@ -95,6 +96,64 @@ void governance_seq_hip(const at::Tensor& admins, at::Tensor oracle_addr, at::Te
   TORCH_CHECK(rc == 0, "svoc_governance failed: ", rc);
 }
 
+// governance_track: governance / governance_seq over an engine that keeps a per-oracle track record (track.hpp).
+// An applied replacement clears the seat's record; min_streak > 0 is the failing-only replacement rule.
+// `order` as in governance_seq (the device applies each instance's run in order), or None: one action per instance.
+void prep_track(const at::Tensor& admins, const at::Tensor& rounds, at::Tensor& flagged, at::Tensor& streak,
+                at::Tensor& score, at::Tensor& since, int64_t min_streak, GovState& g) {
+  const auto dev = admins.device();
+  auto chk = [&](const at::Tensor& t, at::ScalarType dt, int64_t n, const char* name) {
+    TORCH_CHECK(t.scalar_type() == dt && t.is_contiguous() && t.numel() == n && t.device() == dev,
+                "governance_track: ", name, ": wrong dtype, shape or device, or not contiguous");
+  };
+  const int64_t BN = (int64_t)g.B * g.N;
+  chk(rounds, at::kInt, g.B, "rounds"); chk(flagged, at::kInt, BN, "flagged"); chk(streak, at::kInt, BN, "streak");
+  chk(score, at::kLong, BN, "score"); chk(since, at::kInt, BN, "since");
+  TORCH_CHECK(min_streak >= 0 && min_streak <= 0x7fffffff, "governance_track: min_streak out of range");
+  g.track_rounds = rounds.data_ptr<int32_t>();
+  g.track_flagged = flagged.data_ptr<int32_t>();
+  g.track_streak = streak.data_ptr<int32_t>();
+  g.track_score = score.data_ptr<int64_t>();
+  g.track_since = since.data_ptr<int32_t>();
+  g.min_streak = (int)min_streak;
+}
+
+void governance_track_cpu(const at::Tensor& admins, at::Tensor oracle_addr, at::Tensor votes, at::Tensor prop_tag,
+                          at::Tensor prop_idx, at::Tensor prop_addr, const at::Tensor& inst, const at::Tensor& caller,
+                          const at::Tensor& kind, const at::Tensor& arg0, const at::Tensor& arg1, const at::Tensor& addr,
+                          bool enable, int64_t majority, const c10::optional<at::Tensor>& order, at::Tensor status,
+                          at::Tensor applied, const at::Tensor& rounds, at::Tensor flagged, at::Tensor streak,
+                          at::Tensor score, at::Tensor since, int64_t min_streak) {
+  (void)order;   // the CPU applies the whole list in order (instances are independent)
+  TORCH_CHECK(admins.device().is_cpu(), "governance_track: admins must be a host tensor here");
+  GovState g{}; GovAction a{};
+  prep(admins, oracle_addr, votes, prop_tag, prop_idx, prop_addr, inst, caller, kind, arg0, arg1, addr, status,
+       applied, enable, majority, g, a);
+  prep_track(admins, rounds, flagged, streak, score, since, min_streak, g);
+  for (int k = 0; k < a.K; ++k) a.status[k] = gov_apply_one(g, a, k);  // in order
+}
+
+void governance_track_hip(const at::Tensor& admins, at::Tensor oracle_addr, at::Tensor votes, at::Tensor prop_tag,
+                          at::Tensor prop_idx, at::Tensor prop_addr, const at::Tensor& inst, const at::Tensor& caller,
+                          const at::Tensor& kind, const at::Tensor& arg0, const at::Tensor& arg1, const at::Tensor& addr,
+                          bool enable, int64_t majority, const c10::optional<at::Tensor>& order, at::Tensor status,
+                          at::Tensor applied, const at::Tensor& rounds, at::Tensor flagged, at::Tensor streak,
+                          at::Tensor score, at::Tensor since, int64_t min_streak) {
+  TORCH_CHECK(admins.device().is_cuda(), "governance_track: admins must be on the device of the other tensors");
+  GovState g{}; GovAction a{};
+  prep(admins, oracle_addr, votes, prop_tag, prop_idx, prop_addr, inst, caller, kind, arg0, arg1, addr, status,
+       applied, enable, majority, g, a);
+  prep_track(admins, rounds, flagged, streak, score, since, min_streak, g);
+  if (order.has_value() && order->defined()) {
+    TORCH_CHECK(order->scalar_type() == at::kLong && order->is_contiguous() && order->numel() == inst.numel() &&
+                order->device() == admins.device(), "order: contiguous int64 [K]");
+    a.order = order->data_ptr<int64_t>();
+  }
+  auto stream = c10::hip::getCurrentHIPStream(admins.device().index()).stream();
+  const int rc = svoc_governance(&g, &a, stream);
+  TORCH_CHECK(rc == 0, "svoc_governance failed: ", rc);
+}
+
 // find_address: batched find_oracle_index / admin lookup (address_lookup.hpp).  Writes `out` in place: no
 // allocation and no host synchronisation, so a captured graph replays it.
 AddrLookup prep_lookup(const at::Tensor& table, const at::Tensor& inst, const at::Tensor& addr, at::Tensor& out) {
@@ -149,16 +208,24 @@ void register_governance_defs(torch::Library& m) {
       "Tensor(d!) prop_idx, Tensor(e!) prop_addr, Tensor inst, Tensor caller, Tensor kind, Tensor arg0, "
       "Tensor arg1, Tensor addr, bool enable, int majority, Tensor order, Tensor(f!) status, "
       "Tensor(g!) applied) -> ()");
+  m.def(
+      "governance_track(Tensor admins, Tensor(a!) oracle_addr, Tensor(b!) votes, Tensor(c!) prop_tag, "
+      "Tensor(d!) prop_idx, Tensor(e!) prop_addr, Tensor inst, Tensor caller, Tensor kind, Tensor arg0, "
+      "Tensor arg1, Tensor addr, bool enable, int majority, Tensor? order, Tensor(f!) status, "
+      "Tensor(g!) applied, Tensor rounds, Tensor(h!) flagged, Tensor(i!) streak, Tensor(j!) score, "
+      "Tensor(k!) since, int min_streak) -> ()");
   m.def("find_address(Tensor table, Tensor inst, Tensor addr, Tensor(a!) out) -> ()");
 }
 void register_governance_cpu(torch::Library& m) {
   m.impl("governance", &governance_cpu);
   m.impl("governance_seq", &governance_seq_cpu);
+  m.impl("governance_track", &governance_track_cpu);
   m.impl("find_address", &find_address_cpu);
 }
 void register_governance_hip(torch::Library& m) {
   m.impl("governance", &governance_hip);
   m.impl("governance_seq", &governance_seq_hip);
+  m.impl("governance_track", &governance_track_hip);
   m.impl("find_address", &find_address_hip);
 }
 

@@ -286,6 +286,7 @@ void register_extra_defs(torch::Library& m) {
   register_io_defs(m);
   register_bookkeeping_defs(m);
   register_encoder_defs(m);
+  register_track_defs(m);
 }
 
 void register_extra_cpu(torch::Library& m) {
@@ -296,6 +297,7 @@ void register_extra_cpu(torch::Library& m) {
   register_generator_cpu(m);
   register_bookkeeping_cpu(m);
   register_encoder_cpu(m);
+  register_track_cpu(m);
 }
 
 void register_extra_hip(torch::Library& m) {
@@ -306,6 +308,7 @@ void register_extra_hip(torch::Library& m) {
   register_generator_hip(m);
   register_bookkeeping_hip(m);
   register_encoder_hip(m);
+  register_track_hip(m);
 }
 
 }  // namespace svoc

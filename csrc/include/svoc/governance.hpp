@@ -6,6 +6,8 @@
 //   votes[b][r]  : uint64, bit e set <=> vote_matrix[emitter e][receiver r] (column-packed)
 //   prop_tag[b][r] (0 None / 1 Some), prop_idx[b][r], prop_addr[b][r][4]
 // Every action is a transaction: on a revert nothing is written (the vote bit included).
+// With a track record (track.hpp) an applied replacement clears the seat's counters, and min_streak > 0
+// holds a majority vote back until the seat has been flagged min_streak rounds in a row.
 #pragma once
 
 #include <stdint.h>
@@ -25,6 +27,14 @@ struct GovState {
   int B, A, N;
   int enable;              // enable_oracle_replacement
   int majority;            // required_majority
+  // per-oracle track record (track.hpp; nullptr: the instance keeps none) and the failing-only replacement
+  // rule: a replacement applies only to a seat whose streak has reached min_streak (0: rule off)
+  const int32_t* track_rounds;  // [B]
+  int32_t* track_flagged;       // [B, N]
+  int32_t* track_streak;        // [B, N]
+  int64_t* track_score;         // [B, N]
+  int32_t* track_since;         // [B, N]
+  int min_streak;
 };
 
 struct GovAction {         // batched actions, one per instance in a launch
@@ -95,10 +105,22 @@ SVOC_HD int gov_apply_one(const GovState& g, const GovAction& act, int k) {
   }
   if (!g.prop_tag[b * g.A + w]) return ST_UNWRAP_NONE;  // unwrap() on None: revert (vote dropped)
   const int o = g.prop_idx[b * g.A + w];
+  if (g.min_streak > 0 && g.track_streak[b * g.N + o] < g.min_streak) {
+    // the seat is not failing (yet): the vote stands and nothing is replaced or reset -- "if a proposition get
+    // enough vote, but the oracle is not replaceable yet it will be necessary to vote again" (contract.cairo:719)
+    votes[w] = nv;
+    return ST_OK;
+  }
   for (int j = 0; j < 4; ++j) g.oracle_addr[(b * g.N + o) * 4 + j] = g.prop_addr[(b * g.A + w) * 4 + j];
   for (int a = 0; a < g.A; ++a) {  // reinitialize propositions and the vote matrix
     votes[a] = 0;
     g.prop_tag[b * g.A + a] = 0;
+  }
+  if (g.track_streak) {  // the new occupant does not inherit the seat's record
+    g.track_flagged[b * g.N + o] = 0;
+    g.track_streak[b * g.N + o] = 0;
+    g.track_score[b * g.N + o] = 0;
+    g.track_since[b * g.N + o] = g.track_rounds[b];
   }
   if (act.applied) act.applied[k] = 1;
   return ST_OK;

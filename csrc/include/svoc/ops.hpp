@@ -24,4 +24,7 @@ void register_bookkeeping_hip(torch::Library& m);
 void register_encoder_defs(torch::Library& m);
 void register_encoder_cpu(torch::Library& m);
 void register_encoder_hip(torch::Library& m);
+void register_track_defs(torch::Library& m);
+void register_track_cpu(torch::Library& m);
+void register_track_hip(torch::Library& m);
 }  // namespace svoc

@@ -18,6 +18,8 @@ def main(argv=None):
     ap.add_argument("--db", default=None, help="SQLite corpus (reference schema)")
     ap.add_argument("--encoder", default="tiny", choices=["tiny", "base"])
     ap.add_argument("--refresh", type=float, default=5.0, help="auto_fetch period in seconds (client/common.py:11)")
+    ap.add_argument("--track", action="store_true", default=False,
+                    help="keep a per-oracle track record (the failing_oracles command)")
     ap.add_argument("-c", "--command", action="append", default=[], help="run a command and exit")
     ap.add_argument("--web", action="store_true", help="serve the browser UI instead (python -m svoc.web)")
     ap.add_argument("--port", type=int, default=8080)
@@ -31,7 +33,7 @@ def main(argv=None):
         args += ["--disable_startup_fetch"] if a.disable_startup_fetch else []
         return web_main(args)
     cl = Client(device=a.device, mode=a.mode, db_path=a.db, encoder=a.encoder, dimension=a.dimension,
-                refresh_rate=a.refresh, scraper_source=a.scraper_source)
+                refresh_rate=a.refresh, scraper_source=a.scraper_source, track=a.track)
     cl.flags["scraper"] = a.scraper
     cl.flags["live_mode"] = a.live_mode
     if a.command:

@@ -26,8 +26,12 @@ class ConsensusService:
                  storage=None):
         self.cfg = cfg
         self.engine = ConsensusEngine(cfg, batch, device=device, mode=mode, storage=storage)
+        e = self.engine
+        track = ({"rounds": e.track_rounds, "flagged": e.track_flagged, "streak": e.track_streak,
+                  "score": e.track_score, "since": e.track_since} if cfg.track_oracles else None)
         self.gov = Governance(batch, cfg.n_admins, cfg.n_oracles, device, cfg.enable_oracle_replacement,
-                              cfg.required_majority)
+                              cfg.required_majority, track=track, min_streak=cfg.replace_only_failing,
+                              join=e.pipeline_join)
         self.gov.set_addresses(admins, oracles)
         self.B = batch
 
@@ -114,6 +118,18 @@ class ConsensusService:
         instance): status [K] int32 (svoc.status.Status codes) and applied [K] uint8, on the device."""
         return self.gov.submit_batch(inst, caller, kind, arg0, arg1, addr)
 
+    # ---- track record ---------------------------------------------------------------------------
+    def track_record(self):
+        """The per-oracle track record (``cfg.track_oracles``): :meth:`ConsensusEngine.track_record`."""
+        return self.engine.track_record()
+
+    def failing_oracles(self, min_streak: int = 1) -> torch.Tensor:
+        """[B, N] bool on the device: the seats flagged unreliable in each of their instance's last
+        ``min_streak`` committed rounds -- the seats ``replace_only_failing = min_streak`` lets a vote replace."""
+        if int(min_streak) < 1:
+            raise ValueError("min_streak must be >= 1")
+        return self.engine.track_record()["streak"] >= int(min_streak)
+
     def handle(self, b: int) -> "OracleConsensus":
         return OracleConsensus._from_service(self, b)
 
@@ -123,13 +139,15 @@ class OracleConsensus:
 
     def __init__(self, admins: Sequence[int], enable_oracle_replacement: bool, required_majority: int,
                  n_failing_oracles: int, constrained: bool, unconstrained_max_spread: int, dimension: int,
-                 oracles: Sequence[int], device="cpu", mode: str = "exact", storage=None):
+                 oracles: Sequence[int], device="cpu", mode: str = "exact", storage=None, *,
+                 track_oracles: bool = False, replace_only_failing: int = 0):
         ms = felt_to_i128(int(unconstrained_max_spread))
         cfg = ConsensusConfig(n_oracles=len(oracles), dimension=dimension, n_failing_oracles=n_failing_oracles,
                               constrained=bool(constrained), unconstrained_max_spread=ms / WSAD,
                               n_admins=len(admins), required_majority=required_majority,
                               enable_oracle_replacement=bool(enable_oracle_replacement),
-                              unconstrained_max_spread_wsad=ms)
+                              unconstrained_max_spread_wsad=ms, track_oracles=bool(track_oracles),
+                              replace_only_failing=int(replace_only_failing))
         self._max_spread_wsad = ms
         self._svc = ConsensusService(cfg, 1, list(admins), list(oracles), device=device, mode=mode, storage=storage)
         self._b = 0
@@ -226,6 +244,23 @@ class OracleConsensus:
         if not self._svc.gov.enable:
             raise ConsensusRevert(Status.REPLACEMENT_DISABLED, "replacement disabled")
         return self._svc.gov.propositions(self._b)[which_admin]
+
+    # ---- track record (not in the reference ABI) --------------------------------------------------
+    def get_oracle_track_record(self) -> List[Tuple[int, int, int, int]]:
+        """Per oracle seat: (rounds_seated, flagged, streak, mean_score) -- the committed rounds since the seat's
+        occupant took it, how many of them flagged it unreliable, how many of the latest in a row, and its mean
+        per-round score ``1 - qr_i / max qr`` as an int (wsad in exact mode, 2^-32 units in fast mode; truncated;
+        0 before the first round)."""
+        rec = {k: v[self._b].cpu().tolist() for k, v in self._svc.track_record().items()}
+        out = []
+        for fl, sk, sc, si in zip(rec["flagged"], rec["streak"], rec["score"], rec["since"]):
+            seated = rec["rounds"] - si
+            out.append((seated, fl, sk, sc // seated if seated > 0 else 0))
+        return out
+
+    def get_failing_oracles(self, min_streak: int = 1) -> List[int]:
+        """Indices of the seats flagged unreliable in each of the last ``min_streak`` committed rounds."""
+        return [i for i, f in enumerate(self._svc.failing_oracles(min_streak)[self._b].cpu().tolist()) if f]
 
     # ---- north-star aliases ----------------------------------------------------------------------
     def get_consensus(self) -> List[int]:

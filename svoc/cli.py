@@ -51,6 +51,7 @@ Commands :
     - (S) dimension
     - (S) replacement_menu
     - (S) replacement_propositions
+    - (S) failing_oracles [k]             [oracles unreliable in each of the last k rounds (default 1); needs --track]
     - (S) update_proposition <caller_admin> None
     - (S) update_proposition <caller_admin> <old_oracle> <new_oracle>
     - (S) vote_for_a_proposition <caller_admin> <which_admin> yes/no
@@ -68,7 +69,7 @@ class Client:
     def __init__(self, device: str = "cpu", mode: str = "exact", db_path: Optional[str] = None,
                  encoder: str = "tiny", dimension: int = DIMENSION, seed: int = 0,
                  refresh_rate: float = SIMULATION_REFRESH_RATE, emit: Callable[[str], None] = print,
-                 scraper_source: Optional[str] = None):
+                 scraper_source: Optional[str] = None, track: bool = False, replace_only_failing: int = 0):
         self.device = device
         self.scraper_source = scraper_source
         self.refresh_rate = float(refresh_rate)
@@ -81,7 +82,8 @@ class Client:
         self.admins = [codec.shortstring(x) for x in ("Akashi", "Ozu", "Higuchi")]
         self.oracles = [codec.shortstring(f"oracle_{i:02d}") for i in range(N_ORACLES)]
         self.contract = OracleConsensus(self.admins, True, 2, N_FAILING, True, 0, dimension, self.oracles,
-                                        device=device, mode=mode)
+                                        device=device, mode=mode, track_oracles=bool(track),
+                                        replace_only_failing=int(replace_only_failing))
         self.dimension = dimension
         self.db_path = db_path or os.path.join(tempfile.mkdtemp(prefix="svoc_"), "db.sqlite")
         self.conn = corpus.init_db(self.db_path)
@@ -207,6 +209,19 @@ class Client:
              f"kurtosis: {self._fmt(c.get_kurtosis())}"]
         return "\n".join(s)
 
+    def failing_oracles(self, k: int = 1) -> str:
+        """The oracles flagged unreliable in each of the last ``k`` committed rounds, with their track record (the
+        list the reference's replacement menu was meant to get: client/web_interface.py:149 passes it empty)."""
+        c = self.contract
+        if not c.engine.tracking:
+            return "error: no track record (start with --track)"
+        rec, addrs = c.get_oracle_track_record(), c.get_oracle_list()
+        unit = 1e6 if c.engine.mode == "exact" else 2.0 ** 32
+        lines = [f"oracle {i} ({hex(addrs[i])}): unreliable for {rec[i][2]} round(s) in a row, "
+                 f"{rec[i][1]} of {rec[i][0]} in all, mean score {rec[i][3] / unit:.3f}"
+                 for i in c.get_failing_oracles(k)]
+        return "\n".join(lines) if lines else f"no oracle has been unreliable for {k} round(s) in a row"
+
     def query(self, text: str) -> str:
         sp = text.split()
         if sp and sp[0] == "auto_fetch" and len(sp) == 2:   # outside the lock: it may join the loop
@@ -244,6 +259,8 @@ class Client:
         try:
             if cmd in simple:
                 return simple[cmd]()
+            if cmd == "failing_oracles" and len(args) <= 1:
+                return self.failing_oracles(int(args[0]) if args else 1)
             if cmd in ("auto_commit", "auto_resume", "scraper", "live_mode") and args:
                 return onoff(cmd)
             if cmd == "update_proposition" and len(args) in (2, 3):

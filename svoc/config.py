@@ -29,6 +29,12 @@ class ConsensusConfig:
     # contract/obsolete/src/contract_nd.cairo; "1d_legacy" = contract_1d_constrained.cairo (D = 1,
     # constrained).  The obsolete ones compute no moments and no /D in the constrained reliability.
     variant: str = "nds"
+    # per-oracle track record (svoc.engine, csrc/include/svoc/track.hpp): rounds / flagged / streak / score
+    # per seat, updated after every committed round.  Off by default (no state, no launch).
+    track_oracles: bool = False
+    # failing-only replacement (documentation/README.md:114,167-172): a voted replacement applies only to a
+    # seat flagged unreliable in its last k committed rounds; 0 = off.  Needs track_oracles.
+    replace_only_failing: int = 0
 
     def validate(self) -> None:
         if self.n_oracles < 1 or self.dimension < 1:
@@ -41,6 +47,10 @@ class ConsensusConfig:
             raise ValueError(f"unknown contract variant {self.variant!r}")
         if self.variant == "1d_legacy" and (self.dimension != 1 or not self.constrained):
             raise ValueError("the 1-D obsolete contract is constrained with dimension 1")
+        if int(self.replace_only_failing) < 0:
+            raise ValueError("replace_only_failing must be >= 0")
+        if int(self.replace_only_failing) > 0 and not self.track_oracles:
+            raise ValueError("replace_only_failing needs track_oracles (the rule reads the track record)")
 
     @property
     def legacy(self) -> bool:

@@ -8,6 +8,8 @@ mirrors its ``Storage`` struct (contract.cairo:80-102) as tensors with a leading
     n_active[B]           n_active_oracles            consensus_active[B]
     consensus[B, D]       consensus_value             rel[B, 2]        first / second pass reliability
     skew[B, D], kurt[B, D]
+    track_rounds[B], track_flagged / track_streak / track_score / track_since[B, N]
+                          the per-oracle track record (only with ``cfg.track_oracles``; not contract storage)
 
 Two numeric modes share one semantics:
 
@@ -198,6 +200,15 @@ class ConsensusEngine:
         # health counters folded in by every round's epilogue: [rel2 sum (2^-32 units fast / wsad
         # exact), committed, processed, reverted]
         self.metrics_fx = torch.zeros(4, dtype=torch.int64, device=dev)
+        # per-oracle track record (cfg.track_oracles; csrc/include/svoc/track.hpp): updated by one launch after
+        # every round, before its epilogue, for the instances whose round committed
+        self.tracking = bool(cfg.track_oracles)
+        if self.tracking:
+            self.track_rounds = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.track_flagged = torch.zeros(B, N, dtype=torch.int32, device=dev)
+            self.track_streak = torch.zeros(B, N, dtype=torch.int32, device=dev)
+            self.track_score = torch.zeros(B, N, dtype=torch.int64, device=dev)
+            self.track_since = torch.zeros(B, N, dtype=torch.int32, device=dev)
 
     # ------------------------------------------------------------------ sizing
     @staticmethod
@@ -214,7 +225,41 @@ class ConsensusEngine:
 
     def state_bytes_per_instance(self) -> int:
         """bytes_per_instance for this engine's own mode and storage dtype."""
-        return self.bytes_per_instance(self.N, self.D, self.mode, self.storage)
+        n = self.bytes_per_instance(self.N, self.D, self.mode, self.storage)
+        if self.tracking:   # rounds + (flagged, streak, since: int32; score: int64) per oracle
+            n += 4 + self.N * (4 + 4 + 4 + 8)
+        return n
+
+    # ------------------------------------------------------------------ track record
+    def _track_update(self, sl: slice = slice(None), active=None, status=None) -> None:
+        """The round just run over the instances ``sl`` -> the track record (no-op unless ``cfg.track_oracles``):
+        one launch on the current stream, between the round kernel and its epilogue."""
+        if not self.tracking:
+            return
+        self._ops.track_update(self._active[sl] if active is None else active,
+                               self.status[sl] if status is None else status, self.reliable[sl], self.qr[sl],
+                               self.track_rounds[sl], self.track_flagged[sl], self.track_streak[sl],
+                               self.track_score[sl])
+
+    def track_record(self) -> Dict[str, torch.Tensor]:
+        """The per-oracle track record (``cfg.track_oracles``), the engine's own tensors: ``rounds`` [B] committed
+        rounds; per seat [B, N] ``flagged`` (committed rounds it was not reliable in), ``streak`` (how many of the
+        latest in a row), ``score`` (sum of 1 - qr_i / max qr per round: wsad in exact mode, 2^-32 units in fast
+        mode) and ``since`` (``rounds`` when the seat's occupant took it: its rounds are ``rounds - since``)."""
+        if not self.tracking:
+            raise RuntimeError("no track record: the engine was built without cfg.track_oracles")
+        self.pipeline_join()
+        return {"rounds": self.track_rounds, "flagged": self.track_flagged, "streak": self.track_streak,
+                "score": self.track_score, "since": self.track_since}
+
+    def reset_track(self, inst=None) -> None:
+        """Clear the track record of every instance, or of the instances ``inst`` (indices)."""
+        rec = self.track_record()
+        for t in rec.values():
+            if inst is None:
+                t.zero_()
+            else:
+                t[torch.as_tensor(inst, dtype=torch.int64, device=self.device).reshape(-1)] = 0
 
     # ------------------------------------------------------------------ updates
     def _as_storage(self, vals: torch.Tensor) -> torch.Tensor:
@@ -304,6 +349,7 @@ class ConsensusEngine:
                                   self.cfg.max_spread_wsad, self.c1, self.consensus, self.skew, self.kurt,
                                   self.rel, self.qr, self.reliable, self.status, self.cfg.legacy,
                                   stats=self._xstats)
+        self._track_update()
         self._ops.round_epilogue(self._active, self.status, self.rel, self.consensus_active, self.touched,
                                  self.metrics_fx)
         self.rounds += 1
@@ -332,6 +378,7 @@ class ConsensusEngine:
             self._ops.fast_round(*args)
             if restore is not None:
                 self._restore([restore])
+        self._track_update(sl)
         self._ops.round_epilogue(self._active[sl], self.status[sl], self.rel[sl], self.consensus_active[sl],
                                  self.touched[sl], self.metrics_fx)
 
@@ -394,6 +441,7 @@ class ConsensusEngine:
                              self.reliable[sl], self.status[sl], self.wave_hint, 0, 0, self.cfg.legacy, w,
                              self._net_fb, rows, oracle.contiguous(), st, U)
         self._ops.commit_updates(rows, oracle, st, self.values[sl], U)
+        self._track_update(sl)
         self._ops.round_epilogue(self._active[sl], self.status[sl], self.rel[sl], self.consensus_active[sl],
                                  self.touched[sl], self.metrics_fx)
 
@@ -575,7 +623,12 @@ class ConsensusEngine:
 
         These conditions must match ``svoc_exact_verdict_applies`` (csrc/kernels/consensus_wsad.hip) and the
         switches the binding reads (``SVOC_EXACT_I128``, ``SVOC_EXACT_WSAD_MIN_D``): where they differ the results
-        stay right, since ``exact_verdict`` then runs full rounds, but every wave pays one."""
+        stay right, since ``exact_verdict`` then runs full rounds, but every wave pays one.
+
+        Never with ``cfg.track_oracles``: the track record needs every transaction's ``reliable`` mask and
+        ``qr``, which a verdict round does not compute, so a tracking engine runs one full round per wave."""
+        if self.tracking:
+            return False
         if os.environ.get("SVOC_VERDICT_WAVES", "1") == "0":
             return False
         if os.environ.get("SVOC_EXACT_I128", "0")[:1] == "1":

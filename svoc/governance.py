@@ -12,6 +12,13 @@ a vote call to be applied even with required_majority = 1 (§2.8-9); a majority 
 proposition reverts (§2.8-7); replacement keeps the oracle's value / enabled / reliable flags
 (§2.8-6).  Hardening (documented deviation): ``which_admin >= n_admins`` reverts with
 WRONG_ADMIN_INDEX instead of writing an unchecked storage key (§2.8-8).
+
+Track record (``track=``: the engine's ``track_*`` tensors, svoc.engine): an applied replacement clears the
+seat's counters and sets ``since`` to the instance's round count -- the new occupant does not inherit the old
+one's record.  ``min_streak = k > 0`` is the failing-only replacement rule the reference documents and never
+builds (documentation/README.md:114,167-172; contract.cairo:719-720): a vote that reaches the majority on a
+seat whose streak is below ``k`` is stored and returns OK with ``applied = 0``; nothing is replaced or reset,
+and a later vote applies once the seat has been flagged ``k`` rounds in a row.
 """
 from __future__ import annotations
 
@@ -28,9 +35,17 @@ PROPOSE, VOTE = 0, 1
 
 
 class Governance:
-    def __init__(self, B: int, n_admins: int, n_oracles: int, device, enable: bool = True, majority: int = 2):
+    def __init__(self, B: int, n_admins: int, n_oracles: int, device, enable: bool = True, majority: int = 2,
+                 track: Optional[dict] = None, min_streak: int = 0, join=None):
         if n_admins > 64:
             raise ValueError("at most 64 admins")
+        if int(min_streak) < 0 or (int(min_streak) > 0 and track is None):
+            raise ValueError("min_streak needs a track record (and must be >= 0)")
+        # the engine's track tensors (rounds, flagged, streak, score, since) or None; ``join``: called before an
+        # action reads them (the engine's rounds may still be running on side streams)
+        self.track = track
+        self.min_streak = int(min_streak)
+        self._join = join
         self.B, self.A, self.N = B, n_admins, n_oracles
         self.enable = bool(enable)
         self.majority = int(majority)
@@ -152,6 +167,9 @@ class Governance:
             return status, applied
         order = (torch.sort(inst, stable=True).indices if d.type != "cpu"
                  else torch.arange(K, dtype=torch.int64))
+        if self.track is not None:
+            self._run_tracked(inst, caller, kind, arg0, arg1, addr, order, status, applied)
+            return status, applied
         self._ops.governance_seq(self.admins, self.oracle_addr, self.votes, self.prop_tag, self.prop_idx,
                                  self.prop_addr, inst, caller, kind, arg0, arg1, addr, self.enable, self.majority,
                                  order, status, applied)
@@ -162,9 +180,21 @@ class Governance:
         K = inst.numel()
         st = torch.empty(K, dtype=torch.int32, device=self.device)
         ap = torch.zeros(K, dtype=torch.uint8, device=self.device)
+        if self.track is not None:
+            self._run_tracked(inst, caller, kind, arg0, arg1, addr, None, st, ap)
+            return st, ap
         self._ops.governance(self.admins, self.oracle_addr, self.votes, self.prop_tag, self.prop_idx,
                              self.prop_addr, inst, caller, kind, arg0, arg1, addr, self.enable, self.majority, st, ap)
         return st, ap
+
+    def _run_tracked(self, inst, caller, kind, arg0, arg1, addr, order, status, applied) -> None:
+        if self._join is not None:
+            self._join()
+        t = self.track
+        self._ops.governance_track(self.admins, self.oracle_addr, self.votes, self.prop_tag, self.prop_idx,
+                                   self.prop_addr, inst, caller, kind, arg0, arg1, addr, self.enable, self.majority,
+                                   order, status, applied, t["rounds"], t["flagged"], t["streak"], t["score"],
+                                   t["since"], self.min_streak)
 
     # ------------------------------------------------------------------ getters
     def propositions(self, b: int) -> List[Optional[Tuple[int, int]]]:

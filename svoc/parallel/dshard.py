@@ -87,6 +87,7 @@ def _commit(e, sh, active: torch.Tensor, status: torch.Tensor, qr=None, c1=None)
     e.qr.copy_(torch.where(ok1, qr, e.qr))
     e.reliable.copy_(torch.where(ok1, sh.reliable, e.reliable))
     e.c1.copy_(torch.where(ok1, c1, e.c1))
+    e._track_update(active=active, status=status)   # (the global qr / reliable: every rank's replica alike)
     e._ops.round_epilogue(active, status, e.rel, e.consensus_active, e.touched, e.metrics_fx)
 
 

@@ -263,6 +263,23 @@ def consensus_round(values: Sequence[Sequence[int]], n_failing: int, constrained
     return RoundResult(c1, qr, [i for i, _ in ordered], reliable, consensus, rel1, rel2, skew, kurt)
 
 
+def wrap_i64(x: int) -> int:
+    """An integer as an int64 holds it (two's complement truncation)."""
+    x &= (1 << 64) - 1
+    return x - (1 << 64) if x >> 63 else x
+
+
+def track_score(q: int, qmax: int) -> int:
+    """Per-round oracle score in wsad, documentation/README.md:366-370: ``1 - |c_i - e|^2 / max_i |c_i - e|^2``
+    = ``WSAD - wsad_div(q, qmax)`` on int64 quadratic risks.  ``qmax <= 0`` (nobody deviates, or a truncated
+    sum): WSAD for everyone; a negative (truncated) ``q``: 0."""
+    if qmax <= 0:
+        return WSAD
+    if q < 0:
+        return 0
+    return WSAD - (q * WSAD + qmax // 2) // qmax
+
+
 # ----------------------------------------------------------------------------------------------
 # L3/L4: the whole contract as a state machine, ABI names kept (contract.cairo:4-35, 586-831)
 # ----------------------------------------------------------------------------------------------
@@ -284,7 +301,19 @@ class ReferenceContract:
     def __init__(self, admins: Sequence[int], enable_oracle_replacement: bool,
                  required_majority: int, n_failing_oracles: int, constrained: bool,
                  unconstrained_max_spread: int, dimension: int, oracles: Sequence[int],
-                 legacy: bool = False):
+                 legacy: bool = False, *, track_oracles: bool = False, replace_only_failing: int = 0):
+        if replace_only_failing < 0 or (replace_only_failing > 0 and not track_oracles):
+            raise ValueError("replace_only_failing needs track_oracles (and must be >= 0)")
+        # per-oracle track record and the failing-only replacement rule (not in the contract; see
+        # track_score / _track_update / _vote)
+        self.track_oracles = bool(track_oracles)
+        self.replace_only_failing = int(replace_only_failing)
+        n = len(oracles)
+        self.track_rounds = 0
+        self.track_flagged = [0] * n
+        self.track_streak = [0] * n
+        self.track_score = [0] * n
+        self.track_since = [0] * n
         # constructor, contract.cairo:235-265 (legacy: contract/obsolete/src/contract_nd.cairo)
         self.legacy = bool(legacy)
         self.dimension = dimension
@@ -349,7 +378,23 @@ class ReferenceContract:
         self.skewness, self.kurtosis = r.skewness, r.kurtosis
         self.consensus_active_flag = True
         self.last_round = r
+        if self.track_oracles:
+            self._track_update(r)
         return Status.OK
+
+    def _track_update(self, r: "RoundResult") -> None:
+        """One committed round -> the track record: the seats outside the reliable set are flagged, and every
+        seat earns ``track_score(qr_i, max qr)``.  ``qr`` is taken as the engine stores it (int64)."""
+        qr = [wrap_i64(q) for q in r.qr]
+        qmax = max(qr)
+        self.track_rounds += 1
+        for i, rel in enumerate(r.reliable):
+            if rel:
+                self.track_streak[i] = 0
+            else:
+                self.track_flagged[i] += 1
+                self.track_streak[i] += 1
+            self.track_score[i] += track_score(qr[i], qmax)
 
     def update_proposition(self, caller: int, proposition: Optional[Tuple[int, int]]) -> None:
         """contract.cairo:661-717."""
@@ -395,7 +440,15 @@ class ReferenceContract:
         if prop is None:
             raise ConsensusRevert(Status.UNWRAP_NONE, "unwrap on None proposition")
         oracle_idx, new_addr = prop
+        if self.replace_only_failing > 0 and self.track_streak[oracle_idx] < self.replace_only_failing:
+            # failing-only replacement: the seat has not been flagged k rounds in a row, so the vote stands and
+            # nothing is replaced -- "it will be necessary to vote again" (contract.cairo:719-720)
+            return False
         self.oracles[oracle_idx].address = new_addr   # value/enabled/reliable kept (§2.8-6)
+        if self.track_oracles:   # the new occupant does not inherit the seat's record
+            self.track_flagged[oracle_idx] = self.track_streak[oracle_idx] = 0
+            self.track_score[oracle_idx] = 0
+            self.track_since[oracle_idx] = self.track_rounds
         na = len(self.admins)
         self.propositions = [None] * na
         self.vote_matrix = [[False] * na for _ in range(na)]

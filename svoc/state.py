@@ -52,6 +52,9 @@ def save(svc, path: str) -> None:
         ("status", e.status, ""),
         ("touched", e.touched, ""),   # instances whose stored updates still await their round
     ]
+    if e.tracking:
+        # the per-oracle track record (cfg.track_oracles; not contract storage)
+        secs += [("track_" + k, v, "") for k, v in e.track_record().items()]
     if e.mode == "fast" and e._pending:
         # update batches awaiting their round (transactional steps): the pre-image their revert restores
         e._pending.fold()
@@ -113,6 +116,11 @@ def load(path: str, device="cpu"):
     e.rounds = int(meta.get("rounds", 0))
     if "touched" in t:
         e.touched.copy_(t["touched"].to(dev))
+    if e.tracking:
+        # (a checkpoint written without tracking, loaded under a config that tracks: the record starts empty)
+        for k, v in e.track_record().items():
+            if "track_" + k in t:
+                v.copy_(t["track_" + k].to(dev, v.dtype))
     if "pending_pre_values" in t and e.mode == "fast":
         pv = e.values.clone()
         pv[:, :, : e.D].copy_(t["pending_pre_values"].to(dev, e.vdtype))
