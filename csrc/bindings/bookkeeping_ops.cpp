@@ -13,6 +13,13 @@ extern "C" int svoc_bench_marker(int* flag, int code, hipStream_t stream);
 namespace svoc {
 namespace {
 
+// Every tensor of a call lives on the first argument's device, checked before any pointer is taken: the
+// dispatcher picks the HIP implementation when ANY argument is a device tensor, and a kernel must never read
+// through a host pointer.
+void check_dev(const at::Tensor& t, const at::Device& dev, const char* n) {
+  TORCH_CHECK(t.device() == dev, "round bookkeeping: ", n, " must be on ", dev, " (got ", t.device(), ")");
+}
+
 void check_u8(const at::Tensor& t, int64_t B, const char* n) {
   TORCH_CHECK((t.scalar_type() == at::kByte || t.scalar_type() == at::kBool) && t.numel() == B && t.is_contiguous(),
               n, ": uint8/bool [B] contiguous");
@@ -21,6 +28,8 @@ void check_u8(const at::Tensor& t, int64_t B, const char* n) {
 RoundBook make_prologue(const at::Tensor& n_active, at::Tensor& touched, int64_t N, bool only_touched,
                         at::Tensor& active) {
   const int64_t B = n_active.numel();
+  check_dev(touched, n_active.device(), "touched");
+  check_dev(active, n_active.device(), "active");
   TORCH_CHECK(n_active.scalar_type() == at::kInt && n_active.is_contiguous(), "n_active: int32 [B]");
   check_u8(touched, B, "touched");
   check_u8(active, B, "active");
@@ -37,6 +46,10 @@ RoundBook make_prologue(const at::Tensor& n_active, at::Tensor& touched, int64_t
 RoundBook make_epilogue(at::Tensor& active, const at::Tensor& status, const at::Tensor& rel,
                         at::Tensor& consensus_active, at::Tensor& touched, const c10::optional<at::Tensor>& acc) {
   const int64_t B = active.numel();
+  const auto dev = active.device();
+  check_dev(status, dev, "status"); check_dev(rel, dev, "rel");
+  check_dev(consensus_active, dev, "consensus_active"); check_dev(touched, dev, "touched");
+  if (acc.has_value()) check_dev(*acc, dev, "acc");
   check_u8(active, B, "active");
   check_u8(consensus_active, B, "consensus_active");
   check_u8(touched, B, "touched");
@@ -83,6 +96,7 @@ void epilogue_cpu(at::Tensor active, const at::Tensor& status, const at::Tensor&
 }
 
 void prologue_hip(const at::Tensor& n_active, at::Tensor touched, int64_t N, bool only_touched, at::Tensor active) {
+  TORCH_CHECK(n_active.device().is_cuda(), "round_prologue: n_active must be on the device of the other tensors");
   RoundBook r = make_prologue(n_active, touched, N, only_touched, active);
   const int rc = svoc_round_prologue(&r, c10::hip::getCurrentHIPStream(n_active.device().index()).stream());
   TORCH_CHECK(rc == 0, "svoc_round_prologue failed: ", rc);
@@ -90,6 +104,7 @@ void prologue_hip(const at::Tensor& n_active, at::Tensor touched, int64_t N, boo
 
 void epilogue_hip(at::Tensor active, const at::Tensor& status, const at::Tensor& rel, at::Tensor consensus_active,
                   at::Tensor touched, const c10::optional<at::Tensor>& acc) {
+  TORCH_CHECK(active.device().is_cuda(), "round_epilogue: active must be on the device of the other tensors");
   RoundBook r = make_epilogue(active, status, rel, consensus_active, touched, acc);
   const int rc = svoc_round_epilogue(&r, c10::hip::getCurrentHIPStream(active.device().index()).stream());
   TORCH_CHECK(rc == 0, "svoc_round_epilogue failed: ", rc);

@@ -17,8 +17,13 @@ namespace {
 void prep(const at::Tensor& admins, at::Tensor& oracle_addr, at::Tensor& votes, at::Tensor& prop_tag,
           at::Tensor& prop_idx, at::Tensor& prop_addr, const at::Tensor& inst, const at::Tensor& caller,
           const at::Tensor& kind, const at::Tensor& arg0, const at::Tensor& arg1, const at::Tensor& addr,
-          at::Tensor& status, at::Tensor& applied, bool enable, int64_t majority, GovState& g, GovAction& a) {
-  auto chk = [](const at::Tensor& t, at::ScalarType dt, const char* n) {
+          at::Tensor& status, at::Tensor& applied, bool enable, int64_t majority, GovState& g, GovAction& a,
+          const at::Tensor* order = nullptr) {
+  // every tensor on admins' device, checked before any pointer is taken: the dispatcher picks the HIP
+  // implementation when ANY argument is a device tensor, and a kernel must never read through a host pointer
+  const auto dev = admins.device();
+  auto chk = [&](const at::Tensor& t, at::ScalarType dt, const char* n) {
+    TORCH_CHECK(t.device() == dev, "governance: ", n, " must be on ", dev, " (got ", t.device(), ")");
     TORCH_CHECK(t.scalar_type() == dt && t.is_contiguous(), n, ": wrong dtype or not contiguous");
   };
   chk(admins, at::kLong, "admins"); chk(oracle_addr, at::kLong, "oracle_addr");
@@ -26,6 +31,10 @@ void prep(const at::Tensor& admins, at::Tensor& oracle_addr, at::Tensor& votes, 
   chk(prop_addr, at::kLong, "prop_addr"); chk(inst, at::kLong, "inst"); chk(caller, at::kLong, "caller");
   chk(kind, at::kInt, "kind"); chk(arg0, at::kInt, "arg0"); chk(arg1, at::kLong, "arg1"); chk(addr, at::kLong, "addr");
   chk(status, at::kInt, "status"); chk(applied, at::kByte, "applied");
+  if (order) {
+    chk(*order, at::kLong, "order");
+    TORCH_CHECK(order->numel() == inst.numel(), "order: contiguous int64 [K]");
+  }
   TORCH_CHECK(admins.dim() == 3 && admins.size(2) == 4, "admins: [B, A, 4]");
   TORCH_CHECK(oracle_addr.dim() == 3 && oracle_addr.size(2) == 4, "oracle_addr: [B, N, 4]");
   g.B = (int)admins.size(0); g.A = (int)admins.size(1); g.N = (int)oracle_addr.size(1);
@@ -46,6 +55,7 @@ void prep(const at::Tensor& admins, at::Tensor& oracle_addr, at::Tensor& votes, 
   a.inst = inst.data_ptr<int64_t>(); a.caller = caller.data_ptr<int64_t>(); a.kind = kind.data_ptr<int32_t>();
   a.arg0 = arg0.data_ptr<int32_t>(); a.arg1 = arg1.data_ptr<int64_t>(); a.addr = addr.data_ptr<int64_t>();
   a.status = status.data_ptr<int32_t>(); a.applied = applied.data_ptr<uint8_t>(); a.K = (int)K;
+  if (order) a.order = order->data_ptr<int64_t>();
 }
 
 void governance_cpu(const at::Tensor& admins, at::Tensor oracle_addr, at::Tensor votes, at::Tensor prop_tag,
@@ -62,6 +72,8 @@ void governance_hip(const at::Tensor& admins, at::Tensor oracle_addr, at::Tensor
                     at::Tensor prop_idx, at::Tensor prop_addr, const at::Tensor& inst, const at::Tensor& caller,
                     const at::Tensor& kind, const at::Tensor& arg0, const at::Tensor& arg1, const at::Tensor& addr,
                     bool enable, int64_t majority, at::Tensor status, at::Tensor applied) {
+  TORCH_CHECK(admins.device().is_cuda(), "governance: admins must be on the device of the other tensors (got ",
+              admins.device(), ")");
   GovState g{}; GovAction a{};
   prep(admins, oracle_addr, votes, prop_tag, prop_idx, prop_addr, inst, caller, kind, arg0, arg1, addr, status,
        applied, enable, majority, g, a);
@@ -76,21 +88,22 @@ void governance_seq_cpu(const at::Tensor& admins, at::Tensor oracle_addr, at::Te
                         at::Tensor prop_idx, at::Tensor prop_addr, const at::Tensor& inst, const at::Tensor& caller,
                         const at::Tensor& kind, const at::Tensor& arg0, const at::Tensor& arg1, const at::Tensor& addr,
                         bool enable, int64_t majority, const at::Tensor& order, at::Tensor status, at::Tensor applied) {
-  (void)order;   // the CPU applies the whole list in order (instances are independent)
-  governance_cpu(admins, oracle_addr, votes, prop_tag, prop_idx, prop_addr, inst, caller, kind, arg0, arg1, addr,
-                 enable, majority, status, applied);
+  GovState g{}; GovAction a{};
+  prep(admins, oracle_addr, votes, prop_tag, prop_idx, prop_addr, inst, caller, kind, arg0, arg1, addr, status,
+       applied, enable, majority, g, a, &order);
+  // `order` is checked and then left unused: the CPU applies the whole list in order (instances are independent)
+  for (int k = 0; k < a.K; ++k) a.status[k] = gov_apply_one(g, a, k);
 }
 
 void governance_seq_hip(const at::Tensor& admins, at::Tensor oracle_addr, at::Tensor votes, at::Tensor prop_tag,
                         at::Tensor prop_idx, at::Tensor prop_addr, const at::Tensor& inst, const at::Tensor& caller,
                         const at::Tensor& kind, const at::Tensor& arg0, const at::Tensor& arg1, const at::Tensor& addr,
                         bool enable, int64_t majority, const at::Tensor& order, at::Tensor status, at::Tensor applied) {
+  TORCH_CHECK(admins.device().is_cuda(), "governance_seq: admins must be on the device of the other tensors (got ",
+              admins.device(), ")");
   GovState g{}; GovAction a{};
   prep(admins, oracle_addr, votes, prop_tag, prop_idx, prop_addr, inst, caller, kind, arg0, arg1, addr, status,
-       applied, enable, majority, g, a);
-  TORCH_CHECK(order.scalar_type() == at::kLong && order.is_contiguous() && order.numel() == inst.numel(),
-              "order: contiguous int64 [K]");
-  a.order = order.data_ptr<int64_t>();
+       applied, enable, majority, g, a, &order);
   auto stream = c10::hip::getCurrentHIPStream(admins.device().index()).stream();
   const int rc = svoc_governance(&g, &a, stream);
   TORCH_CHECK(rc == 0, "svoc_governance failed: ", rc);

@@ -14,7 +14,7 @@ import torch
 
 from .. import ops as svops
 from .corpus import BOOTSTRAPING_SUBSET, WINDOW_SIZE
-from .encoder import ORACLE_LABEL_IDX, EncoderConfig, SentimentEncoder, build
+from .encoder import GO_EMOTIONS, ORACLE_LABEL_IDX, EncoderConfig, SentimentEncoder, build
 
 
 class SentimentOraclePipeline:
@@ -25,6 +25,10 @@ class SentimentOraclePipeline:
         self.encoder = encoder if encoder is not None else build(dev, torch.bfloat16 if dev.type == "cuda"
                                                                  else torch.float32, seed, enc_cfg)
         self.window, self.subset = window, subset
+        # the bootstrap op reads scores[..., label_idx] without a range check (it stays free of host
+        # synchronisation so that a captured graph replays it): the indices are checked here, on the host list
+        if not all(0 <= int(i) < len(GO_EMOTIONS) for i in ORACLE_LABEL_IDX):
+            raise ValueError("oracle label index outside the 28 go_emotions scores")
         self.label_idx = torch.tensor(ORACLE_LABEL_IDX, dtype=torch.int32, device=dev)
         self.seed = seed
         self.fetches = 0

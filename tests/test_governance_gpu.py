@@ -1,9 +1,11 @@
-"""Batched governance kernel (csrc/kernels/governance.hip) vs the in-order CPU implementation."""
+"""Batched governance kernels (csrc/kernels/governance.hip) vs the in-order CPU implementation and, for the
+cases of tests/gov_cases.py, vs the golden contract (one svoc.reference.ReferenceContract per instance)."""
 import random
 
 import pytest
 import torch
 
+import gov_cases as gc
 from svoc.governance import Governance
 
 pytestmark = pytest.mark.gpu
@@ -120,3 +122,76 @@ def test_governance_service_one_million_mixed_actions():
         res[dev] = (st.cpu(), ap.cpu(), svc.gov.votes.cpu(), svc.gov.oracle_addr.cpu())
     for x, y in zip(res["cpu"], res["cuda"]):
         assert torch.equal(x, y)
+
+
+# ---- the golden contract as the reference (tests/gov_cases.py; the CPU ops meet it in test_governance_model.py)
+def _gov_for(built):
+    return Governance(built.B, built.A, built.N, "cuda", True, built.majority)
+
+
+@pytest.mark.parametrize("shape", gc.SHAPES, ids=gc.shape_id)
+def test_random_case_gpu_matches_golden(shape):
+    """submit_batch (device sort + governance_seq): 3000 mixed actions over 3-8 instances with full-width
+    addresses one limb apart, 1 to 64 admins; statuses, applied flags and the whole state against one
+    ReferenceContract per instance."""
+    built = gc.random_case(shape)
+    gc.check_ordered(_gov_for(built), built)
+
+
+def test_directed_majority_64_gpu_matches_golden():
+    """A = 64, majority 64: the 64th vote applies (bit 63 of the column last, or first and withdrawn), a majority
+    on a None proposition reverts without storing the bit, one-limb-away addresses, instances outside [0, B)."""
+    built = gc.directed_case()
+    gc.check_ordered(_gov_for(built), built)
+
+
+def test_empty_batch_gpu():
+    built = gc.empty_case()
+    gc.check_ordered(_gov_for(built), built)
+    gc.check_unordered(_gov_for(built), built)
+
+
+@pytest.mark.parametrize("shape", gc.SHAPES, ids=gc.shape_id)
+def test_unique_slice_gpu_matches_golden(shape):
+    """submit_tensors (the unordered governance op, one lane per action): 640 unique instances in shuffled order,
+    a proposition everywhere and then the deciding vote, each launch against the golden."""
+    built = gc.slice_case(shape)
+    gc.check_unordered(_gov_for(built), built)
+
+
+def test_governance_ops_refuse_a_host_tensor_among_device_tensors():
+    """The dispatcher takes the HIP path when any argument is a device tensor; the bindings refuse the call before
+    a kernel could read through a host pointer (every tensor position of both ops, the order included)."""
+    built = gc.empty_case()
+    g = gc.setup(_gov_for(built), built)
+    ad = built.addr
+    acts = gc.action_tensors([gc.Action(b, ad.admins[b][0], gc.PROPOSE, 1, 0, ad.spares[b][0]) for b in range(built.B)])
+    a = {k: v.cuda() for k, v in acts.items()}
+    K = built.B
+    status = torch.full((K,), -1, dtype=torch.int32, device="cuda")
+    applied = torch.zeros(K, dtype=torch.uint8, device="cuda")
+    order = torch.arange(K, dtype=torch.int64, device="cuda")
+    state = [g.admins, g.oracle_addr, g.votes, g.prop_tag, g.prop_idx, g.prop_addr]
+    tensors = state + [a[n] for n in ("inst", "caller", "kind", "arg0", "arg1", "addr")]
+    ops = torch.ops.svoc
+
+    def call(seq, t, order, status, applied):
+        if seq:
+            ops.governance_seq(*t, True, g.majority, order, status, applied)
+        else:
+            ops.governance(*t, True, g.majority, status, applied)
+
+    for seq in (False, True):
+        for k in range(len(tensors)):
+            with pytest.raises(RuntimeError):
+                call(seq, [(t.cpu() if i == k else t) for i, t in enumerate(tensors)], order, status, applied)
+        with pytest.raises(RuntimeError):
+            call(seq, tensors, order, status.cpu(), applied)
+        with pytest.raises(RuntimeError):
+            call(seq, tensors, order, status, applied.cpu())
+    with pytest.raises(RuntimeError):
+        call(True, tensors, order.cpu(), status, applied)
+    torch.cuda.synchronize()
+    assert (status == -1).all() and not g.prop_tag.any() and not g.votes.any()
+    call(True, tensors, order, status, applied)            # the same call with every tensor on the device runs
+    assert (status.cpu() == 0).all() and g.prop_tag[:, 0].cpu().tolist() == [1] * K
