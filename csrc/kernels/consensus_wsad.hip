@@ -1027,6 +1027,10 @@ void consensus_wsad_kernel(ExactParams p) {
     }
     if (vc && !ok_sd) dz = true;   // sqrt(0) -> wsad_div by 0, sqrt(1) divides by 0: DIV_BY_ZERO
     if constexpr (VERDICT) continue;   // (the z-powers and the moments' arithmetic cannot fail otherwise)
+    // a column without an sd has no z-scores: every row reads as the mean (z = 0, all sums 0).  With the
+    // placeholder sd = 1 a variance-1 column gave z ~ 1e9, the range guards below flagged the round, and the
+    // i128 kernel had to name the DIV_BY_ZERO this kernel had already found (flag is read before div0)
+    if (!ok_sd) mm = 0ull;
     // z = wsad_div(x - mu, sd) = I128Div((x - mu) 1e6 + floor(sd / 2), sd): A = x 1e6 + C0 (exact integers
     // below 2^51), then the half-offset forms of wsad_fast.hpp -- no remainder tests in the row loop
     const double isd = 1.0 / sd, hisd = 0.5 * isd;

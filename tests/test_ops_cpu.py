@@ -53,6 +53,8 @@ def test_exact_cpu_matches_python_random(constrained):
         o = run_exact(torch.tensor([vals], dtype=torch.int64), f, constrained, ms)
         assert o["status"].item() == int(st_ref), (N, D, f, vals)
         if st_ref == Status.OK:
+            assert o["c1"][0].tolist() == r.c1
+            assert o["qr"][0].tolist() == r.qr
             assert o["consensus"][0].tolist() == r.consensus
             assert o["rel"][0].tolist() == [r.rel1, r.rel2]
             assert o["skew"][0].tolist() == r.skewness

@@ -1,6 +1,7 @@
 """Shared helpers of the wide-column exact kernel's GPU tests (test_wsadx_gpu.py, test_wsadx_groups_gpu.py,
-test_wsadx_sharded_gpu.py; csrc/kernels/consensus_wsadx.hip): the env-guarded op caller, the input recipes and the
-contract's arithmetic in Python integers."""
+test_wsadx_sharded_gpu.py; csrc/kernels/consensus_wsadx.hip): the env-guarded op caller (also the caller of the
+model-pinned tests, exact_cases.py), the input recipes and the contract's arithmetic in Python integers."""
+import contextlib
 import os
 
 import torch
@@ -17,9 +18,28 @@ PATTERN = {"c1": -101, "consensus": -102, "skew": -103, "kurt": -104, "rel": -10
            "status": -1}
 
 
-def _run(values, f, env=None, ms=MS, mode=0, rel_dim=0, inp=None, prefill=False, active=None):
+@contextlib.contextmanager
+def _switches(env):
+    """The exact ops' environment switches set to `env` alone for the launch, then put back."""
+    old = {k: os.environ.get(k) for k in ("SVOC_EXACT_I128", "SVOC_EXACT_WSAD_ONLY", "SVOC_EXACT_WSAD_MIN_D")}
+    try:
+        for k in old:
+            os.environ.pop(k, None)
+        os.environ.update(env or {})
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def _run(values, f, env=None, ms=MS, mode=0, rel_dim=0, inp=None, prefill=False, active=None, constrained=False,
+         legacy=False, verdict=False):
     """One launch of exact_round in `mode`; `prefill`: over outputs filled with PATTERN (an unwanted write shows);
-    `inp`: the inputs of the half (mode 2: c1, qr, status) copied over them first."""
+    `inp`: the inputs of the half (mode 2: c1, qr, status) copied over them first.  `verdict`: exact_verdict instead
+    (status and rel are its outputs; `vstats` its routing counters)."""
     B, N, D = values.shape
     o = alloc_exact_out(B, N, D, values.device)
     if prefill:
@@ -28,25 +48,21 @@ def _run(values, f, env=None, ms=MS, mode=0, rel_dim=0, inp=None, prefill=False,
     for k, t in (inp or {}).items():
         o[k].copy_(t.to(values.device))
     stats = torch.zeros(2, dtype=torch.int32, device=values.device) if values.is_cuda else None
+    vstats = torch.zeros(3, dtype=torch.int32, device=values.device) if values.is_cuda and verdict else None
     if active is not None:
         active = active.to(values.device)
-    old = {k: os.environ.get(k) for k in ("SVOC_EXACT_I128", "SVOC_EXACT_WSAD_ONLY", "SVOC_EXACT_WSAD_MIN_D")}
-    try:
-        for k in old:
-            os.environ.pop(k, None)
-        os.environ.update(env or {})
-        svops.ops().exact_round(values, active, f, False, ms, o["c1"], o["consensus"], o["skew"], o["kurt"], o["rel"],
-                                o["qr"], o["reliable"], o["status"], False, mode, rel_dim, stats=stats)
+    with _switches(env):
+        if verdict:
+            svops.ops().exact_verdict(values, active, f, constrained, ms, o["rel"], o["status"], legacy, stats=stats,
+                                      vstats=vstats)
+        else:
+            svops.ops().exact_round(values, active, f, constrained, ms, o["c1"], o["consensus"], o["skew"], o["kurt"],
+                                    o["rel"], o["qr"], o["reliable"], o["status"], legacy, mode, rel_dim, stats=stats)
         if values.is_cuda:
             torch.cuda.synchronize()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
     out = {k: v.cpu() for k, v in o.items()}
     out["stats"] = stats.cpu().tolist() if stats is not None else None
+    out["vstats"] = vstats.cpu().tolist() if vstats is not None else None
     return out
 
 
