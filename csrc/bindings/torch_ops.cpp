@@ -67,12 +67,17 @@ void fast_round_cpu(const at::Tensor& values, const c10::optional<at::Tensor>& a
                     const c10::optional<at::Tensor>& upd_rows, const c10::optional<at::Tensor>& upd_oracle,
                     const c10::optional<at::Tensor>& upd_status, int64_t upd_per_inst,
                     const c10::optional<at::Tensor>& rst_saved, const c10::optional<at::Tensor>& rst_saved_en,
-                    const c10::optional<at::Tensor>& rst_enabled, const c10::optional<at::Tensor>& rst_n_active) {
+                    const c10::optional<at::Tensor>& rst_enabled, const c10::optional<at::Tensor>& rst_n_active,
+                    const c10::optional<at::Tensor>& pend_rows, const c10::optional<at::Tensor>& pend_oracle,
+                    const c10::optional<at::Tensor>& pend_status) {
   (void)wave_hint;
   (void)work;
   (void)stats;   // (GPU pruned-network counter; the CPU twin runs full sorts)
   TORCH_CHECK(!upd_rows.has_value() || !upd_rows->defined(), "fused transactional streaming is a GPU path");
   TORCH_CHECK(!rst_saved.has_value() || !rst_saved->defined(), "in-kernel rollback is a GPU path");
+  TORCH_CHECK(!pend_rows.has_value() || !pend_rows->defined(), "the deferred commit is a GPU path");
+  (void)pend_oracle;
+  (void)pend_status;
   (void)rst_saved_en;
   (void)rst_enabled;
   (void)rst_n_active;
@@ -127,7 +132,9 @@ void fast_round_hip(const at::Tensor& values, const c10::optional<at::Tensor>& a
                     const c10::optional<at::Tensor>& upd_rows, const c10::optional<at::Tensor>& upd_oracle,
                     const c10::optional<at::Tensor>& upd_status, int64_t upd_per_inst,
                     const c10::optional<at::Tensor>& rst_saved, const c10::optional<at::Tensor>& rst_saved_en,
-                    const c10::optional<at::Tensor>& rst_enabled, const c10::optional<at::Tensor>& rst_n_active) {
+                    const c10::optional<at::Tensor>& rst_enabled, const c10::optional<at::Tensor>& rst_n_active,
+                    const c10::optional<at::Tensor>& pend_rows, const c10::optional<at::Tensor>& pend_oracle,
+                    const c10::optional<at::Tensor>& pend_status) {
   fast_round_checks(values, D, c1, cons, skew, kurt, rel, qr, reliable, status);
   TORCH_CHECK(values.scalar_type() == at::kBFloat16 || values.scalar_type() == at::kFloat,
               "GPU fast path stores values in bf16 or fp32");
@@ -224,6 +231,27 @@ void fast_round_hip(const at::Tensor& values, const c10::optional<at::Tensor>& a
     p.upd_oracle = upd_oracle->data_ptr<int64_t>();
     p.upd_status = upd_status->data_ptr<int32_t>();
     p.upd_per_inst = (int)upd_per_inst;
+    if (pend_rows.has_value() && pend_rows->defined()) {
+      // deferred commit (launch.hpp FastParams.pend_rows): the previous launch's batch over the same instances
+      TORCH_CHECK(pend_oracle.has_value() && pend_oracle->defined() && pend_status.has_value() && pend_status->defined(),
+                  "deferred commit: pend_oracle and pend_status go with pend_rows");
+      TORCH_CHECK(upd_per_inst <= 127 && D % 4 == 0, "deferred commit: at most 127 updates per instance, D % 4 == 0");
+      TORCH_CHECK(pend_rows->scalar_type() == values.scalar_type() && pend_rows->is_contiguous() && pend_rows->dim() == 2 &&
+                      pend_rows->size(0) == n && pend_rows->size(1) == D && pend_rows->device() == values.device(),
+                  "pend_rows: contiguous [B * U, D] in the values' dtype on the values' device");
+      TORCH_CHECK(pend_oracle->scalar_type() == at::kLong && pend_oracle->is_contiguous() && pend_oracle->numel() == n &&
+                      pend_oracle->device() == values.device(),
+                  "pend_oracle: contiguous int64 [B * U]");
+      TORCH_CHECK(pend_status->scalar_type() == at::kInt && pend_status->is_contiguous() && pend_status->numel() == n &&
+                      pend_status->device() == values.device(),
+                  "pend_status: contiguous int32 [B * U]");
+      TORCH_CHECK(pend_status->data_ptr() != upd_status->data_ptr(), "pend_status: not the buffer this launch writes");
+      p.pend_rows = (const float*)pend_rows->data_ptr();
+      p.pend_oracle = pend_oracle->data_ptr<int64_t>();
+      p.pend_status = pend_status->data_ptr<int32_t>();
+    }
+  } else {
+    TORCH_CHECK(!(pend_rows.has_value() && pend_rows->defined()), "pend_rows: only with the fused path's upd_rows");
   }
   if (rst_saved.has_value() && rst_saved->defined()) {
     // in-kernel rollback of the generic transactional path (launch.hpp FastParams.rst_saved): the update
@@ -511,7 +539,8 @@ TORCH_LIBRARY(svoc, m) {
       "Tensor(g!) reliable, Tensor(h!) status, int wave_hint=0, int mode=0, int rel_dim=0, bool legacy=False, "
       "Tensor? work=None, Tensor(i!)? stats=None, Tensor? upd_rows=None, Tensor? upd_oracle=None, "
       "Tensor(j!)? upd_status=None, int upd_per_inst=0, Tensor? rst_saved=None, Tensor? rst_saved_en=None, "
-      "Tensor(k!)? rst_enabled=None, Tensor(l!)? rst_n_active=None) -> ()");
+      "Tensor(k!)? rst_enabled=None, Tensor(l!)? rst_n_active=None, Tensor? pend_rows=None, "
+      "Tensor? pend_oracle=None, Tensor? pend_status=None) -> ()");
   m.def(
       "exact_round(Tensor values, Tensor? active, int n_failing, bool constrained, int max_spread, "
       "Tensor(a!) c1, Tensor(b!) consensus, Tensor(c!) skew, Tensor(d!) kurt, Tensor(e!) rel, Tensor(f!) qr, "

@@ -49,6 +49,15 @@ struct FastParams {
   const int64_t* upd_oracle;
   int32_t* upd_status;
   int upd_per_inst;
+  // Deferred commit of the fused path (null pend_rows = off): the PREVIOUS launch's batch over the same
+  // instances (same U and pitch) with the statuses that launch wrote.  Its accepted rows are not in the state
+  // yet: this round reads them from pend_rows (unless the row is updated again by upd_rows) and stores them to
+  // the state on the way -- from the LDS copy of phase A, or at exit for a row whose new update is not
+  // accepted.  After the launch the state holds every accepted row of the pending batch except those replaced
+  // by an accepted row of this batch (which is pending in turn).  Needs U <= 127 and D % 4 == 0.
+  const float* pend_rows;
+  const int64_t* pend_oracle;
+  const int32_t* pend_status;
   // In-kernel rollback of the generic transactional path (bf16 window kernel, mode 0; null rst_saved = off):
   // updates b * rst_U .. b * rst_U + rst_U - 1 of this launch belong to instance b, and the update kernel
   // saved what they overwrote (rst_saved [B * U, D] in the values' dtype, rst_saved_en the old `enabled`

@@ -13,6 +13,7 @@ namespace svoc {
 // The lane's 64 raw rows as two 32-wide vectors (one SSA value each): a plain array is split by SROA into
 // a promoted part and a scratch part when several code paths read it.
 typedef uint32_t u32x32_t __attribute__((ext_vector_type(32)));
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));   // one 16-B DMA piece of a lane
 struct RawRows {
   u32x32_t lo, hi;   // rows 0..31, 32..63
   SVOC_DEV uint32_t at(int i) const { return i < 32 ? lo[i] : hi[i - 32]; }
@@ -100,6 +101,44 @@ struct SlabDma {
           "s_mov_b32 m0, %0"
           : "=&s"(keep), "=&s"(sx)
           : "v"(vo), "v"(vb), "v"(fb), "s"(rs.w), "s"(rb.w), "s"(lds), "s"(k * (RPI / NSEG) * rowb)
+          : "vcc", "memory");
+    }
+  }
+  // issue_mapped with a third source (deferred commit): sel(k) is a SIGNED byte -- 0 the state row, > 0 a row of
+  // the current batch rb, < 0 a row of the pending batch rp -- and off_b(k) the byte offset within whichever
+  // batch.  Three loads per piece under disjoint exec masks; both compares precede the one s_nop.
+  template <class Sel, class OffB>
+  SVOC_DEV void issue_mapped3(const BufDesc& rs, const BufDesc& rb, const BufDesc& rp, uint32_t* region, int rowb,
+                              int col0, Sel sel, OffB off_b) const {
+    const int vo = vlane + col0 * 4;
+    const uint32_t lds0 = lds_addr(region);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const uint32_t lds = lds0 + k * 1024u;
+      const int fb = sel(k);
+      const int vb = off_b(k);
+      int keep;
+      uint64_t sx, sp;
+      asm volatile(
+          "s_mov_b32 %0, m0\n\t"
+          "s_mov_b32 m0, %9\n\t"
+          "s_mov_b64 %1, exec\n\t"
+          "v_cmp_gt_i32_e64 %2, 0, %5\n\t"
+          "v_cmp_lt_i32 vcc, 0, %5\n\t"
+          "s_nop 4\n\t"
+          "s_and_b64 exec, %1, vcc\n\t"
+          "s_nop 0\n\t"
+          "buffer_load_dwordx4 %4, %7, 0 offen lds\n\t"
+          "s_and_b64 exec, %1, %2\n\t"
+          "s_or_b64 vcc, vcc, %2\n\t"
+          "buffer_load_dwordx4 %4, %8, 0 offen lds\n\t"
+          "s_andn2_b64 exec, %1, vcc\n\t"
+          "s_nop 0\n\t"
+          "buffer_load_dwordx4 %3, %6, %10 offen lds\n\t"
+          "s_mov_b64 exec, %1\n\t"
+          "s_mov_b32 m0, %0"
+          : "=&s"(keep), "=&s"(sx), "=&s"(sp)
+          : "v"(vo), "v"(vb), "v"(fb), "s"(rs.w), "s"(rb.w), "s"(rp.w), "s"(lds), "s"(k * (RPI / NSEG) * rowb)
           : "vcc", "memory");
     }
   }

@@ -175,7 +175,7 @@ SVOC_DEV bool try_pruned(uint32_t (&r)[64], int seg, int lane, uint32_t (&w)[WN]
 // network, window, c1 and qr pass run on the registers while it lands.  2 waves per SIMD (<= 256
 // VGPRs: 64 keys + 64 raw rows + the window), LDS = WAVES x 16 KiB.
 
-template <int NSEG, int WAVES, int H, bool CONS, int MODE, bool FUSED = false>
+template <int NSEG, int WAVES, int H, bool CONS, int MODE, bool FUSED = false, bool DEFER = false, bool WIDE = false>
 __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2))) void consensus_fast_winf_kernel(FastParams p) {
   // (no implicit fma contraction: the fused-streaming and plain instantiations compile their arithmetic in
   // different contexts and must still round alike -- tests/test_fast_transactional.py compares them bit for bit)
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
   constexpr int NT = WAVES * 64;
   constexpr int KEEP = 64 / P;
   constexpr bool PASS1 = MODE != 2;
-  __shared__ uint32_t slab[PASS1 ? WAVES * 64 * 64 : 1];   // one 16-KiB DMA region per wave
+  __shared__ __attribute__((aligned(16))) uint32_t slab[PASS1 ? WAVES * 64 * 64 : 1];   // one 16-KiB DMA region per wave
   __shared__ __attribute__((aligned(16))) float qr_part[WAVES * NPAD];   // (then the rank keys: 2 NPAD words)
   __shared__ float qr_lds[NPAD];
   __shared__ uint64_t relmask[4];
@@ -197,10 +197,14 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
   // fused transactional streaming (FastParams.upd_rows): row -> its update's slot in this instance's batch
   // (-1: the state row), and the slots whose row failed the interval check
   __shared__ int smap[FUSED ? NPAD : 1];
+  // deferred commit (FastParams.pend_rows): row -> its accepted update's slot in the pending batch (-1: none)
+  __shared__ int spend[DEFER ? NPAD : 1];
   __shared__ uint32_t badu[8];
 
   const int b = blockIdx.x;
   static_assert(!FUSED || (MODE == 0 && CONS), "fused streaming: whole constrained rounds");
+  static_assert(!DEFER || FUSED, "deferred commit: a mode of the fused path");
+  static_assert(!WIDE || (FUSED && !DEFER), "9-bit piece map: the fused path at 256 updates per instance");
   constexpr bool fused = FUSED;
   const int U = fused ? p.upd_per_inst : 0;
   if (p.active && !p.active[b]) {
@@ -233,8 +237,15 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
   const uint32_t ubytes = fused ? (uint32_t)(U * D * 4) : 0u;
   const __amdgpu_buffer_rsrc_t rb = instance_rsrc(urows, ubytes);
   const BufDesc rbd = buf_desc(urows, ubytes);
+  // the pending batch of this instance (the previous launch's; same U and pitch)
+  const float* prows = DEFER ? p.pend_rows + (int64_t)b * U * D : inst;
+  const __amdgpu_buffer_rsrc_t rp = instance_rsrc(prows, DEFER ? ubytes : 0u);
+  const BufDesc rpd = buf_desc(prows, DEFER ? ubytes : 0u);
   if constexpr (FUSED) {
     for (int t = tid; t < NPAD; t += NT) smap[t] = -1;
+  }
+  if constexpr (DEFER) {
+    for (int t = tid; t < NPAD; t += NT) spend[t] = -1;
   }
   if (tid < 8) badu[tid] = 0u;
   __syncthreads();
@@ -242,12 +253,21 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
     for (int t = tid; t < U; t += NT) {
       const int64_t o = p.upd_oracle[(int64_t)b * U + t];
       if (o >= 0 && o < N) smap[o] = t;
+      if constexpr (DEFER) {
+        const int64_t q = p.pend_oracle[(int64_t)b * U + t];
+        if (q >= 0 && q < N && p.pend_status[(int64_t)b * U + t] == ST_OK) spend[q] = t;
+      }
     }
   __syncthreads();
-  // one value of row `row` (wave-uniform) at byte offset `cb` of the row: batch or state
+  // one value of row `row` (wave-uniform) at byte offset `cb` of the row: batch, pending batch or state (a
+  // pending row's state location is never read: this launch may be writing it)
   auto row_load = [&](int row, int cb) __attribute__((always_inline)) -> uint32_t {
     int u = -1;
     if constexpr (FUSED) u = __builtin_amdgcn_readfirstlane(smap[row]);
+    if constexpr (DEFER) {
+      const int q = __builtin_amdgcn_readfirstlane(spend[row]);
+      if (u < 0 && q >= 0) return bload(rp, cb, q * D * 4);
+    }
     return u >= 0 ? bload(rb, cb, u * D * 4) : bload(rs, cb, row * rowb);
   };
   auto bad_slot = [&](int u) __attribute__((always_inline)) { return (badu[u >> 5] >> (u & 31)) & 1u; };
@@ -271,6 +291,18 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
         }
         p.upd_status[(int64_t)b * U + t] = s;
       }
+    if constexpr (DEFER) {
+      // a pending accepted row that this step updated again was never streamed (so not written back): when
+      // the new update is not accepted either, the pending row is the oracle's value -- stored here (rare)
+      for (int t = wave; t < U; t += WAVES) {
+        const int64_t o = p.upd_oracle[(int64_t)b * U + t];
+        if (o < 0 || o >= N || (st == ST_OK && !bad_slot(t))) continue;   // (uniform)
+        const int q = spend[o];
+        if (q < 0) continue;
+        float* dst = (float*)p.values + (int64_t)b * p.inst_stride + o * (int64_t)p.ld;
+        for (int d = lane; d < D; d += 64) dst[d] = prows[(int64_t)q * D + d];
+      }
+    }
   };
   const int lo1 = (NPAD - N + 1) >> 1;
   const int nv = N - seg * 64;
@@ -297,8 +329,9 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
   // this lane's words: global row seg * 64 + i at LDS row NSEG * i + seg, i.e. word 64 i + seg P + cw
   const uint32_t* const mine = region + (PASS1 ? seg * P + cw : 0);
   // fused: per-piece row sources of this lane's DMA, packed 4 per register (byte k % 4 of pmap[k / 4] =
-  // batch slot + 1 of the piece's row, 0 = the state row); offsets formed at issue
-  uint32_t pmap[FUSED ? 4 : 1] = {};
+  // batch slot + 1 of the piece's row, 0 = the state row); offsets formed at issue.  WIDE (256 updates per
+  // instance: slot + 1 = 256 does not fit the byte): bit k of pmap[4] is bit 8 of piece k's source
+  uint32_t pmap[FUSED ? (WIDE ? 5 : 4) : 1] = {};
   auto map_pieces = [&]() __attribute__((always_inline)) {
     if constexpr (FUSED) {
 #pragma unroll
@@ -306,6 +339,15 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
         const int row = dma.row_of(k);
         const int u = row < N ? smap[row] : -1;
         if (k % 4 == 0) pmap[k / 4] = 0u;
+        if constexpr (DEFER) {
+          // (bit 7: a slot of the pending batch -- a negative byte; U <= 127)
+          const int q = row < N ? spend[row] : -1;
+          pmap[k / 4] |= (uint32_t)(u >= 0 ? u + 1 : q >= 0 ? 0x80 | (q + 1) : 0) << (8 * (k % 4));
+        } else if constexpr (WIDE) {
+          if (k == 0) pmap[4] = 0u;
+          pmap[k / 4] |= (uint32_t)((u + 1) & 0xff) << (8 * (k % 4));
+          pmap[4] |= (uint32_t)((u + 1) >> 8) << k;
+        } else
         pmap[k / 4] |= (uint32_t)(u + 1) << (8 * (k % 4));
       }
     }
@@ -326,6 +368,19 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
       // used: exec-masked.)  Per piece: the byte extract, the multiply-add and the mask compare.
       int cbm = (s * W + wave * P) * 4 + dma.colb - d4;
       asm volatile("" : "+v"(cbm));   // (one v_mad_u32_u24 per piece, not a multiply and two adds)
+      if constexpr (DEFER)
+        dma.issue_mapped3(
+            rsd, rbd, rpd, reg_o, rowb_o, s * W + wave * P,
+            [&](int k) { return (int)(pm[k / 4] << (24 - 8 * (k % 4))) >> 24; },
+            [&](int k) { return (int)__umul24((pm[k / 4] >> (8 * (k % 4))) & 0x7fu, (unsigned)d4) + cbm; });
+      else if constexpr (WIDE) {
+        uint32_t ph = pmap[4];
+        asm volatile("" : "+v"(ph));
+        dma.issue_mapped(
+            rsd, rbd, reg_o, rowb_o, s * W + wave * P,
+            [&](int k) { return ((pm[k / 4] >> (8 * (k % 4))) & 0xffu) | (((ph >> k) & 1u) << 8); },
+            [&](int, uint32_t fb) { return (int)__umul24(fb, (unsigned)d4) + cbm; });
+      } else
       dma.issue_mapped(
           rsd, rbd, reg_o, rowb_o, s * W + wave * P,
           [&](int k) { return (pm[k / 4] >> (8 * (k % 4))) & 0xffu; },
@@ -350,6 +405,37 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
     const uint32_t mW = vc ? 0xffffffffu : 0u;
     RawRows xs;        // the lane's raw rows, kept for the qr pass
     __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): this wave's pieces of slab s have landed
+    if constexpr (DEFER) {
+      // write-back of the pending rows (first attempt): every piece this lane's DMA took from the pending batch
+      // goes from the LDS copy to the state address the state source would have been read from.  (The stores
+      // are in flight during the network; the next slab's vmcnt(0) also waits for them.)
+      if (attempt == 0) {
+        uint32_t pm[4] = {pmap[0], pmap[1], pmap[2], pmap[3]};
+        asm volatile("" : "+v"(pm[0]), "+v"(pm[1]), "+v"(pm[2]), "+v"(pm[3]));
+        int rowb_o = rowb;
+        asm volatile("" : "+s"(rowb_o));
+        const int c0 = s * W + wave * P;
+        const int vo = dma.vlane + c0 * 4;
+        const bool cvalid = FULL || c0 + (dma.colb >> 2) < D;   // (D % 4 == 0: the lane's 4 columns alike)
+        const u32x4_t* piece = reinterpret_cast<const u32x4_t*>(region) + lane;
+        // (8 pieces at a time: the LDS reads issued together ahead of the masked stores -- read inside each
+        // store's branch, every piece waits out its own LDS latency)
+#pragma unroll
+        for (int k0 = 0; k0 < 16; k0 += 8) {
+          u32x4_t pc[8];
+#pragma unroll
+          for (int k = 0; k < 8; ++k) pc[k] = piece[(k0 + k) * 64];
+#pragma unroll
+          for (int k = 0; k < 8; ++k) asm volatile("" : "+v"(pc[k]));
+#pragma unroll
+          for (int k = k0; k < k0 + 8; ++k) {
+            const int fb = (int)(pm[k / 4] << (24 - 8 * (k % 4))) >> 24;
+            if (fb < 0 && cvalid)
+              __builtin_amdgcn_raw_buffer_store_b128(pc[k - k0], rs, vo, k * (SlabDma<NSEG>::RPI / NSEG) * rowb_o, 0);
+          }
+        }
+      }
+    }
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
       xs.lo[i] = mine[i * 64];
@@ -844,9 +930,10 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
         const bool use = i < N && ((relmask[g] >> lane) & 1);
         float xv = 0.f;
         if (use) {
-          int u = -1;
+          int u = -1, q = -1;
           if constexpr (FUSED) u = smap[i];
-          xv = u >= 0 ? urows[(int64_t)u * D + col] : xc[(int64_t)i * p.ld];
+          if constexpr (DEFER) q = spend[i];
+          xv = u >= 0 ? urows[(int64_t)u * D + col] : q >= 0 ? prows[(int64_t)q * D + col] : xc[(int64_t)i * p.ld];
         }
         y[g] = use ? xv - cc : 0.f;
         t1 += y[g];
@@ -957,6 +1044,16 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
 template <int NSEG, int WAVES, int H, bool CONS>
 static void launch_winf_w(const FastParams& p, hipStream_t stream) {
   if constexpr (CONS) {
+    if (p.upd_rows && p.pend_rows) {   // ... with the previous batch's commit deferred into this round
+      hipLaunchKernelGGL((consensus_fast_winf_kernel<NSEG, WAVES, H, CONS, 0, true, true>), dim3(p.B),
+                         dim3(WAVES * 64), 0, stream, p);
+      return;
+    }
+    if (p.upd_rows && p.upd_per_inst > 255) {   // ... with the 9-bit piece map
+      hipLaunchKernelGGL((consensus_fast_winf_kernel<NSEG, WAVES, H, CONS, 0, true, false, true>), dim3(p.B),
+                         dim3(WAVES * 64), 0, stream, p);
+      return;
+    }
     if (p.upd_rows) {   // fused transactional streaming (mode 0)
       hipLaunchKernelGGL((consensus_fast_winf_kernel<NSEG, WAVES, H, CONS, 0, true>), dim3(p.B), dim3(WAVES * 64), 0,
                          stream, p);
@@ -997,6 +1094,8 @@ extern "C" int svoc_fast_round_f32_win(const FastParams* p, hipStream_t stream) 
   if (p->mode == 2 && p->work_fresh) return -2;   // pass 1 ran elsewhere: no windows to read
   if (p->upd_rows && (p->mode != 0 || !p->constrained || p->upd_per_inst <= 0 || p->upd_per_inst > 256 ||
                       (int64_t)p->upd_per_inst * p->D * 4 >= (1ll << 31) || (int64_t)p->ld * 4 >= (1ll << 24)))
+    return -3;
+  if (p->pend_rows && (!p->upd_rows || !p->pend_oracle || !p->pend_status || p->upd_per_inst > 127 || p->D % 4 != 0))
     return -3;
   if (p->n_failing < 0 || p->n_failing > 32 || p->n_failing > p->N - 2) return -2;
   const int H = fast_win_h(p->N, p->n_failing);

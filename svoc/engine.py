@@ -417,19 +417,30 @@ class ConsensusEngine:
             self._all_active = bool((self.n_active == self.N).all())
         return self._all_active
 
-    def _status_buffer(self, U: int) -> torch.Tensor:
-        buf = self._save_bufs.get(("st",))
+    def _status_buffer(self, U: int, slot: int = 0) -> torch.Tensor:
+        """The fused path's update statuses (slot 1: the second buffer of the deferred commit, whose round
+        reads the pending batch's statuses while it writes its own)."""
+        key = ("st",) if slot == 0 else ("st", slot)
+        buf = self._save_bufs.get(key)
         if buf is None or buf.shape[0] < U:
             buf = torch.empty(U, dtype=torch.int32, device=self.device)
-            self._save_bufs[("st",)] = buf
+            self._save_bufs[key] = buf
         return buf[:U]
 
+    def _defer_ok(self, U: int) -> bool:
+        """Whether an open fused step may leave its commit to the next step's round (FastParams.pend_rows: the
+        piece map's pending bit and the 16-B write-back need U <= 127 and D % 4 == 0)."""
+        if os.environ.get("SVOC_DEFERRED_COMMIT", "1") == "0":   # (A/B: the commit kernel after every round)
+            return False
+        return 0 < U <= 127 and self.D % 4 == 0
+
     def _run_round_range_fused(self, b0: int, b1: int, oracle: torch.Tensor, rows: torch.Tensor, st: torch.Tensor,
-                               U: int) -> None:
+                               U: int, pend=None, commit: bool = True) -> None:
         """Fused transactional round over instances [b0, b1): every instance is active and each has U
         updates (rows b * U ..); the window kernel reads the updated rows from `rows`, writes each update's
         transaction status to `st`, and the commit kernel stores the accepted rows (a reverted round's rows
-        never reach the state)."""
+        never reach the state).  Deferred commit: ``commit=False`` leaves the accepted rows to the next round of
+        the range, which gets them as ``pend`` = (rows, oracle, statuses) of that batch and writes them back."""
         sl = slice(b0, b1)
         self._ops.round_prologue(self.n_active[sl], self.touched[sl], self.N, False, self._active[sl])
         w = self.work()
@@ -439,8 +450,10 @@ class ConsensusEngine:
                              self.cfg.constrained, float(self.cfg.unconstrained_max_spread), self.c1[sl],
                              self.consensus[sl], self.skew[sl], self.kurt[sl], self.rel[sl], self.qr[sl],
                              self.reliable[sl], self.status[sl], self.wave_hint, 0, 0, self.cfg.legacy, w,
-                             self._net_fb, rows, oracle.contiguous(), st, U)
-        self._ops.commit_updates(rows, oracle, st, self.values[sl], U)
+                             self._net_fb, rows, oracle.contiguous(), st, U, None, None, None, None,
+                             *(pend if pend is not None else (None, None, None)))
+        if commit:
+            self._ops.commit_updates(rows, oracle, st, self.values[sl], U)
         self._track_update(sl)
         self._ops.round_epilogue(self._active[sl], self.status[sl], self.rel[sl], self.consensus_active[sl],
                                  self.touched[sl], self.metrics_fx)
@@ -461,7 +474,15 @@ class ConsensusEngine:
         k queues behind this call's round of range k (the one kernel that reads those rows) and runs
         beside the other ranges' rounds.  The engine is then "open": :meth:`pipeline_join` (called by
         every other engine method) joins the streams into the current stream before anything else
-        touches the state."""
+        touches the state.
+
+        Pending commit (open pipeline, fused fp32 path, U <= 127, D % 4 == 0; ``SVOC_DEFERRED_COMMIT=0`` turns
+        it off): the accepted rows of an open step are not stored by a commit kernel.  The next open step's
+        round of the same range reads them from the held batch and writes them to ``values`` while it streams
+        the instance; the last open step's rows are stored by the commit kernel at the join.  So between joins
+        ``values`` may lag by one accepted batch per range -- outputs and statuses never do -- and after
+        :meth:`pipeline_join` it is exact.  A step that does not match the pending one (other ``U``, other
+        ranges, not fused) joins first."""
         U = int(updates_per_instance)
         # the batch goes to kernels that dereference it directly (the fused round, the commit and restore
         # kernels): indices as int64 and rows in the storage dtype, all on the state's device
@@ -487,12 +508,19 @@ class ConsensusEngine:
         # and a commit kernel copies the accepted ones -- no saved copy, no restore (_fused_ok)
         fused = self.transactional and self._fused_ok(inst, oracle, vals, U)
         kroll = self.transactional and not fused and self._kernel_rollback_ok(U)
+        # pending commit: this step's accepted rows wait for the next step's round (docstring)
+        defer = fused and overlap and self._defer_ok(U)
+        pend = getattr(self, "_defer", None)
+        if pend is not None and not (defer and pend["U"] == U and pend["ranges"] == ranges):
+            self.pipeline_join()   # flushes the pending batch
+            pend = None
         # per-step buffers live in the engine (the side streams use them after this returns): saved rows,
         # saved enabled flags and the update statuses, one slice per range
         if fused:
             sv_all = sen_all = None
-            st_all = self._status_buffer(inst.numel())
+            st_all = self._status_buffer(inst.numel(), 1 - pend["slot"] if pend is not None else 0)
             vals = vals.contiguous()
+            self._last_st = st_all   # (this step's update statuses: valid once its rounds have run)
         else:
             sv_all, sen_all, st_all = (self._save_buffer(("pipe",), inst.numel()) if self.transactional
                                        else (None,) * 3)
@@ -510,7 +538,8 @@ class ConsensusEngine:
         def rnd(k, b0, b1):
             sl = slice(b0 * U, b1 * U)
             if fused:
-                self._run_round_range_fused(b0, b1, oracle[sl], vals[sl], st_all[sl], U)
+                pk = (pend["rows"][sl], pend["oracle"][sl], pend["st"][sl]) if pend is not None else None
+                self._run_round_range_fused(b0, b1, oracle[sl], vals[sl], st_all[sl], U, pend=pk, commit=not defer)
                 return
             rest = (inst[sl], oracle[sl], st_all[sl], sv_all[sl], sen_all[sl]) if self.transactional else None
             self._run_round_range(b0, b1, restore=rest, U=U if (rest is not None and kroll) else 0)
@@ -535,6 +564,9 @@ class ConsensusEngine:
             held = getattr(self, "_pipe_held", None) or []
             held.append((inst, oracle, vals))
             self._pipe_held = held
+            if defer:
+                self._defer = {"U": U, "ranges": ranges, "rows": vals, "oracle": oracle, "st": st_all,
+                               "slot": 1 - pend["slot"] if pend is not None else 0}
             self.rounds += 1
             self._pipe_open = True
             return
@@ -550,7 +582,8 @@ class ConsensusEngine:
             cur.wait_stream(s)
 
     def pipeline_join(self) -> None:
-        """Join the streams of an open (``overlap=True``) pipelined step into the current stream, and
+        """Join the streams of an open (``overlap=True``) pipelined step into the current stream (storing its
+        pending commit first: the last open step's accepted rows, see :meth:`step_pipelined`), and
         commit a deferred D-sharded round (svoc.parallel.dshard, ``defer=True``): every reader of the
         state (getters, metrics, checkpoints, the next update) goes through here.  With a D-shard round
         pending this is a collective (one status all-reduce): every rank of the shard group must read."""
@@ -562,6 +595,17 @@ class ConsensusEngine:
 
     def _join_streams(self) -> None:
         if getattr(self, "_pipe_open", False):
+            pend = getattr(self, "_defer", None)
+            if pend is not None:
+                # the pending commit's flush: the last open step's accepted rows, by the commit kernel on each
+                # range's stream (behind its round), before the held batch is released
+                U = pend["U"]
+                for k, (b0, b1) in enumerate(pend["ranges"]):
+                    sl = slice(b0 * U, b1 * U)
+                    with torch.cuda.stream(self._pipe_streams[1 + k]):
+                        self._ops.commit_updates(pend["rows"][sl], pend["oracle"][sl], pend["st"][sl],
+                                                 self.values[b0:b1], U)
+                self._defer = None
             cur = torch.cuda.current_stream(self.device)
             for s in self._pipe_streams:
                 cur.wait_stream(s)
