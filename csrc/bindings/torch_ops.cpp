@@ -10,7 +10,7 @@
 #include <thread>
 
 #include "../engine/engine.hpp"
-#include "svoc/launch.hpp"
+#include "svoc/route.hpp"
 #include "svoc/ops.hpp"
 
 namespace svoc {
@@ -156,6 +156,11 @@ void fast_round_hip(const at::Tensor& values, const c10::optional<at::Tensor>& a
     TORCH_CHECK(N * ld * 2 < (1ll << 31) && fast_work_words(D) * 4 < (1ll << 31),
                 "instance too large for 32-bit buffer offsets (N * ld * 2 B and the workspace must stay < 2 GiB)");
   }
+  TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0, 1 or 2");
+  // the kernel this round takes and what it supports (route.hpp), the same function the dispatcher switches on
+  const bool has_work = work.has_value() && work->defined();
+  const FastRoute route = fast_route({f32 ? kStoreF32 : kStoreBf16, (int)N, (int)D, (int)ld, (int)n_failing, constrained,
+                                      legacy, (int)mode, (int)wave_hint, has_work ? kWorkCaller : kWorkNone});
   FastParams p{};
   p.values = values.data_ptr();
   p.active = active_ptr(active, B, values.device());
@@ -165,7 +170,6 @@ void fast_round_hip(const at::Tensor& values, const c10::optional<at::Tensor>& a
   p.constrained = constrained ? 1 : 0;
   p.max_spread = (float)max_spread;
   p.wave_hint = (int)wave_hint;
-  TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0, 1 or 2");
   p.mode = (int)mode;
   p.rel_dim = (int)rel_dim;
   p.legacy = legacy ? 1 : 0;
@@ -185,13 +189,13 @@ void fast_round_hip(const at::Tensor& values, const c10::optional<at::Tensor>& a
   // D-sharded round), else a temporary one for a full round
   at::Tensor wtmp;
   const int64_t words = fast_work_words(D);
-  if (work.has_value() && work->defined()) {
+  if (has_work) {
     TORCH_CHECK(work->is_contiguous() && work->element_size() == 4 && work->device() == values.device(),
                 "work: contiguous 4-byte elements on the values' device");
     TORCH_CHECK(work->numel() >= fast_work_numel(B, D), "work: needs ", fast_work_numel(B, D),
                 " elements (svoc.ops.fast_work_numel)");
     p.work = (uint32_t*)work->data_ptr();
-  } else if (mode != 1 && (f32 || !(mode == 0 && wave_hint == 0 && N <= 16 && D <= 128))) {
+  } else if (route.needs_work) {
     // a temporary one: every kernel but the small-instance one stages its pass-2 outputs there
     wtmp = at::empty({fast_work_numel(B, D)}, values.options().dtype(at::kInt));
     p.work = (uint32_t*)wtmp.data_ptr();
@@ -216,7 +220,9 @@ void fast_round_hip(const at::Tensor& values, const c10::optional<at::Tensor>& a
     TORCH_CHECK(!t->has_value() || !(*t)->defined() || (*t)->device() == values.device(),
                 "fast_round: every update / rollback tensor must be on the values' device");
   if (upd_rows.has_value() && upd_rows->defined()) {
-    TORCH_CHECK(f32 && mode == 0 && constrained, "fused streaming: fp32 storage, whole constrained rounds");
+    TORCH_CHECK(upd_per_inst <= route.fused_max_u, "fused streaming: this round's kernel takes at most ",
+                route.fused_max_u, " updates per instance (fp32 storage, whole constrained rounds on the window "
+                "kernel; svoc.ops.fast_route)");
     TORCH_CHECK(upd_per_inst > 0 && upd_oracle.has_value() && upd_status.has_value(), "fused streaming: "
                 "upd_oracle, upd_status and upd_per_inst > 0 go with upd_rows");
     const int64_t n = B * upd_per_inst;
@@ -235,7 +241,8 @@ void fast_round_hip(const at::Tensor& values, const c10::optional<at::Tensor>& a
       // deferred commit (launch.hpp FastParams.pend_rows): the previous launch's batch over the same instances
       TORCH_CHECK(pend_oracle.has_value() && pend_oracle->defined() && pend_status.has_value() && pend_status->defined(),
                   "deferred commit: pend_oracle and pend_status go with pend_rows");
-      TORCH_CHECK(upd_per_inst <= 127 && D % 4 == 0, "deferred commit: at most 127 updates per instance, D % 4 == 0");
+      TORCH_CHECK(upd_per_inst <= route.defer_max_u, "deferred commit: at most ", route.defer_max_u,
+                  " updates per instance here (D % 4 == 0; svoc.ops.fast_route)");
       TORCH_CHECK(pend_rows->scalar_type() == values.scalar_type() && pend_rows->is_contiguous() && pend_rows->dim() == 2 &&
                       pend_rows->size(0) == n && pend_rows->size(1) == D && pend_rows->device() == values.device(),
                   "pend_rows: contiguous [B * U, D] in the values' dtype on the values' device");
@@ -255,13 +262,11 @@ void fast_round_hip(const at::Tensor& values, const c10::optional<at::Tensor>& a
   }
   if (rst_saved.has_value() && rst_saved->defined()) {
     // in-kernel rollback of the generic transactional path (launch.hpp FastParams.rst_saved): the update
-    // kernel's saved rows / flags and statuses for B * U instance-grouped updates; -3 from the dispatcher when
-    // the kernel that runs cannot do it (the caller then launches svoc_restore_updates)
+    // kernel's saved rows / flags and statuses for B * U instance-grouped updates
     TORCH_CHECK(!(upd_rows.has_value() && upd_rows->defined()), "rst_saved: not with the fused path's upd_rows");
     TORCH_CHECK(mode == 0 && upd_per_inst > 0 && upd_oracle.has_value() && upd_status.has_value() &&
                     rst_saved_en.has_value() && rst_enabled.has_value() && rst_n_active.has_value(),
                 "rst_saved: mode 0, with upd_oracle, upd_status, upd_per_inst, rst_saved_en, rst_enabled, rst_n_active");
-    // (checked before any launch: the rc == -3 fallback below needs it after the plain round has run)
     TORCH_CHECK(active.has_value() && active->defined(), "rst_saved: needs the round's active mask");
     const int64_t n = B * upd_per_inst;
     TORCH_CHECK(rst_saved->scalar_type() == values.scalar_type() && rst_saved->is_contiguous() &&
@@ -277,52 +282,45 @@ void fast_round_hip(const at::Tensor& values, const c10::optional<at::Tensor>& a
                 "rst_enabled: contiguous uint8 [B, N]");
     TORCH_CHECK(rst_n_active->scalar_type() == at::kInt && rst_n_active->is_contiguous() && rst_n_active->numel() == B,
                 "rst_n_active: contiguous int32 [B]");
-    p.rst_saved = rst_saved->data_ptr();
-    p.rst_saved_en = rst_saved_en->data_ptr<uint8_t>();
-    p.rst_oracle = upd_oracle->data_ptr<int64_t>();
-    p.rst_status = upd_status->data_ptr<int32_t>();
-    p.rst_enabled = rst_enabled->data_ptr<uint8_t>();
-    p.rst_n_active = rst_n_active->data_ptr<int32_t>();
-    p.rst_U = (int)upd_per_inst;
-    const int rc = f32 ? svoc_fast_round_f32(&p, stream) : svoc_fast_round_bf16(&p, stream);
-    TORCH_CHECK(rc == 0 || rc == -3, f32 ? "svoc_fast_round_f32" : "svoc_fast_round_bf16", " launch failed: ", rc);
-    if (rc == -3) {
-      // the kernel that runs this round cannot roll back (the dispatcher returns -3 before any launch): the
-      // plain round, then the restore kernel over the same saved batch -- the updates are already stored, so
-      // the round must run and the reverted instances must be rolled back here, not left to the caller
-      p.rst_saved = nullptr;
-      p.rst_saved_en = nullptr;
-      p.rst_oracle = nullptr;
-      p.rst_status = nullptr;
-      p.rst_enabled = nullptr;
-      p.rst_n_active = nullptr;
-      p.rst_U = 0;
-      const int rc2 = f32 ? svoc_fast_round_f32(&p, stream) : svoc_fast_round_bf16(&p, stream);
-      TORCH_CHECK(rc2 == 0, f32 ? "svoc_fast_round_f32" : "svoc_fast_round_bf16", " launch failed: ", rc2);
-      // instance-grouped batch: update u belongs to instance u / U
-      at::Tensor inst = at::arange(n, upd_oracle->options()).div(upd_per_inst, "floor");
-      RestoreParams r{};
-      r.inactive_status = -1;
-      r.values = values.data_ptr();
-      r.enabled = rst_enabled->data_ptr<uint8_t>();
-      r.n_active = rst_n_active->data_ptr<int32_t>();
-      r.inst = inst.data_ptr<int64_t>();
-      r.oracle = upd_oracle->data_ptr<int64_t>();
-      r.upd_status = upd_status->data_ptr<int32_t>();
-      r.saved = rst_saved->data_ptr();
-      r.saved_en = rst_saved_en->data_ptr<uint8_t>();
-      r.status = status.data_ptr<int32_t>();
-      r.active = active->data_ptr<uint8_t>();
-      r.inst_stride = values.stride(0);
-      r.B = (int)B; r.N = (int)N; r.D = (int)D; r.ld = (int)ld; r.U = (int)n;
-      r.elem_bytes = (int)values.element_size();
-      const int rc3 = svoc_restore_updates(&r, stream);
-      TORCH_CHECK(rc3 == 0, "svoc_restore_updates failed: ", rc3);
+    if (route.rollback) {
+      p.rst_saved = rst_saved->data_ptr();
+      p.rst_saved_en = rst_saved_en->data_ptr<uint8_t>();
+      p.rst_oracle = upd_oracle->data_ptr<int64_t>();
+      p.rst_status = upd_status->data_ptr<int32_t>();
+      p.rst_enabled = rst_enabled->data_ptr<uint8_t>();
+      p.rst_n_active = rst_n_active->data_ptr<int32_t>();
+      p.rst_U = (int)upd_per_inst;
     }
-    return;
   }
   const int rc = f32 ? svoc_fast_round_f32(&p, stream) : svoc_fast_round_bf16(&p, stream);
+  // (-3: the dispatcher cannot do what the route said the kernel supports -- the two never disagree)
+  TORCH_CHECK(rc != -3, "fast_round: the route and the dispatcher disagree on this launch (fused batch: ",
+              p.upd_rows != nullptr, ", in-kernel rollback: ", p.rst_saved != nullptr, ")");
   TORCH_CHECK(rc == 0, f32 ? "svoc_fast_round_f32" : "svoc_fast_round_bf16", " launch failed: ", rc);
+  if (rst_saved.has_value() && rst_saved->defined() && !route.rollback) {
+    // the kernel that ran this round cannot roll back: the restore kernel over the same saved batch -- the updates
+    // are already stored, so the reverted instances must be rolled back here, not left to the caller.
+    // Instance-grouped batch: update u belongs to instance u / U
+    const int64_t n = B * upd_per_inst;
+    at::Tensor inst = at::arange(n, upd_oracle->options()).div(upd_per_inst, "floor");
+    RestoreParams r{};
+    r.inactive_status = -1;
+    r.values = values.data_ptr();
+    r.enabled = rst_enabled->data_ptr<uint8_t>();
+    r.n_active = rst_n_active->data_ptr<int32_t>();
+    r.inst = inst.data_ptr<int64_t>();
+    r.oracle = upd_oracle->data_ptr<int64_t>();
+    r.upd_status = upd_status->data_ptr<int32_t>();
+    r.saved = rst_saved->data_ptr();
+    r.saved_en = rst_saved_en->data_ptr<uint8_t>();
+    r.status = status.data_ptr<int32_t>();
+    r.active = active->data_ptr<uint8_t>();
+    r.inst_stride = values.stride(0);
+    r.B = (int)B; r.N = (int)N; r.D = (int)D; r.ld = (int)ld; r.U = (int)n;
+    r.elem_bytes = (int)values.element_size();
+    const int rc3 = svoc_restore_updates(&r, stream);
+    TORCH_CHECK(rc3 == 0, "svoc_restore_updates failed: ", rc3);
+  }
 }
 
 // -------------------------------------------------------------------------------------- exact
@@ -377,22 +375,24 @@ void exact_round_cpu(const at::Tensor& values, const c10::optional<at::Tensor>& 
   exact_round_batch_cpu(eb, cpu_threads());
 }
 
-// the column kernel's environment switches (tests, A/B)
-bool exact_force_i128() {
+// the exact kernels' environment switches (tests, A/B), read here and nowhere else
+struct ExactSwitches {
+  int force_i128;      // SVOC_EXACT_I128=1: the i128 kernel everywhere
+  int skip_fallback;   // SVOC_EXACT_WSAD_ONLY=1: leave the instances the column kernel flags alone
+  int wsad_min_d;      // SVOC_EXACT_WSAD_MIN_D: route small instances through the column kernel too
+};
+ExactSwitches exact_switches() {
   const char* force = std::getenv("SVOC_EXACT_I128");
-  return force && force[0] == '1';
-}
-void column_kernel_switches(ExactParams& p) {
   const char* only = std::getenv("SVOC_EXACT_WSAD_ONLY");
-  p.skip_fallback = only && only[0] == '1';
-  const char* md = std::getenv("SVOC_EXACT_WSAD_MIN_D");   // tests: route small instances through it too
-  p.wsad_min_d = md ? std::atoi(md) : 64;
+  const char* md = std::getenv("SVOC_EXACT_WSAD_MIN_D");
+  return {force && force[0] == '1', only && only[0] == '1', md ? std::atoi(md) : kWsadMinD};
 }
 
 // What exact_round and exact_verdict share on the GPU: the round's inputs and switches in an ExactParams, the i128
 // kernel's workspace, and the column kernel's buffers (the caller sets the output pointers).
 struct ExactLaunch {
   ExactParams p{};
+  ExactRoute route{};
   at::Tensor work, stage, fallback;
 
   ExactLaunch(const at::Tensor& values, const c10::optional<at::Tensor>& active, int64_t n_failing, bool constrained,
@@ -418,21 +418,24 @@ struct ExactLaunch {
       work = at::empty({(int64_t)p.B, kExactWsCols, (int64_t)p.D}, values.options().dtype(at::kLong));
       p.work = work.data_ptr<int64_t>();
     }
+    const ExactSwitches sw = exact_switches();
+    p.skip_fallback = sw.skip_fallback;
+    p.wsad_min_d = sw.wsad_min_d;
+    route = exact_route(exact_shape(p, sw.force_i128));
   }
 
-  // column-parallel kernel (consensus_wsad.hip), the i128 kernel for the instances it flags;
-  // SVOC_EXACT_I128=1 forces the i128 kernel everywhere (tests, A/B)
+  // column-parallel kernel (consensus_wsad.hip) where the route takes the round, the i128 kernel for the
+  // instances it flags
   bool column_kernel(const at::Tensor& values) {
-    if (p.N < 4 || exact_force_i128()) return false;
+    if (!route.column) return false;
     fallback = at::empty({(int64_t)p.B}, values.options().dtype(at::kByte));
     p.fallback = fallback.data_ptr<uint8_t>();
-    column_kernel_switches(p);
     return true;
   }
   // the full column kernel's stage: c1, consensus, skewness, kurtosis; the window keys; unconstrained: the
   // columns' base words
   void alloc_stage(const at::Tensor& values) {
-    p.win_h = p.mode == 0 && p.constrained && !p.legacy ? exact_win_h(p.N, p.n_failing) : 0;
+    p.win_h = route.win_h;
     stage = at::empty({(int64_t)p.B, 4 + 2 * p.win_h + (p.constrained ? 0 : 2), (int64_t)p.D},
                       values.options().dtype(at::kInt));
     p.stage = stage.data_ptr<int32_t>();
@@ -487,6 +490,24 @@ struct ScratchOutputs {
   }
 };
 
+// ---- the routes, for Python (svoc.ops.fast_route / exact_route): tensor-less, the shape as ints
+std::vector<int64_t> fast_route_op(int64_t storage, int64_t N, int64_t D, int64_t ld, int64_t n_failing, bool constrained,
+                                   bool legacy, int64_t mode, int64_t wave_hint, int64_t work) {
+  TORCH_CHECK(N >= 1 && D >= 1 && ld >= D && N < (1ll << 31) && ld < (1ll << 31),
+              "fast_route: 1 <= N, 1 <= D <= ld (int32)");
+  const FastRoute r = fast_route({(int)storage, (int)N, (int)D, (int)ld, (int)n_failing, constrained, legacy, (int)mode,
+                                  (int)wave_hint, (int)work});
+  return {r.kernel, r.lane_groups, r.win_h, r.needs_work, r.pruned, r.rollback, r.fused_max_u, r.defer_max_u};
+}
+std::vector<int64_t> exact_route_op(int64_t N, int64_t D, int64_t elem_bytes, int64_t n_failing, bool constrained,
+                                    bool legacy, int64_t mode) {
+  TORCH_CHECK(N >= 1 && D >= 1 && N < (1ll << 31) && D < (1ll << 31), "exact_route: 1 <= N, D (int32)");
+  const ExactSwitches sw = exact_switches();
+  const ExactRoute r = exact_route({(int)N, (int)D, (int)elem_bytes, (int)n_failing, constrained, legacy, (int)mode,
+                                    sw.wsad_min_d, sw.force_i128});
+  return {r.column, r.lane_groups, r.win_h, r.verdict};
+}
+
 void exact_verdict_cpu(const at::Tensor& values, const c10::optional<at::Tensor>& active, int64_t n_failing,
                        bool constrained, int64_t max_spread, at::Tensor rel, at::Tensor status, bool legacy,
                        const c10::optional<at::Tensor>& stats, const c10::optional<at::Tensor>& vstats) {
@@ -523,7 +544,7 @@ void exact_verdict_hip(const at::Tensor& values, const c10::optional<at::Tensor>
   p.qr = o.qr.data_ptr<int64_t>();
   p.reliable = o.reliable.data_ptr<uint8_t>();
   // (the verdict form has no stage; every other shape runs the full column kernel with its own)
-  if (l.column_kernel(values) && !svoc_exact_verdict_applies(&p)) l.alloc_stage(values);
+  if (l.column_kernel(values) && !l.route.verdict) l.alloc_stage(values);
   auto stream = c10::hip::getCurrentHIPStream(values.device().index()).stream();
   const int rc = svoc_exact_verdict(&p, stream);
   TORCH_CHECK(rc == 0, "svoc_exact_verdict launch failed: ", rc);
@@ -549,6 +570,14 @@ TORCH_LIBRARY(svoc, m) {
   m.def(
       "exact_verdict(Tensor values, Tensor? active, int n_failing, bool constrained, int max_spread, "
       "Tensor(a!) rel, Tensor(b!) status, bool legacy, Tensor(c!)? stats=None, Tensor(d!)? vstats=None) -> ()");
+  // device-independent (pure functions of the shape): catch-all kernels with the schema
+  m.def("fast_route(int storage, int N, int D, int ld, int n_failing, bool constrained, bool legacy, int mode, "
+        "int wave_hint, int work) -> int[]", &svoc::fast_route_op);
+  m.def("exact_route(int N, int D, int elem_bytes, int n_failing, bool constrained, bool legacy, int mode) -> int[]",
+        &svoc::exact_route_op);
+  m.def("fast_work_words(int D) -> int", [](int64_t D) { return svoc::fast_work_words(D); });
+  m.def("fast_win_h(int N, int n_failing) -> int",
+        [](int64_t N, int64_t f) { return (int64_t)svoc::fast_win_h((int)N, (int)f); });
   svoc::register_extra_defs(m);
 }
 

@@ -39,7 +39,7 @@
 #include <utility>
 
 #include "svoc/bufload.hpp"
-#include "svoc/launch.hpp"
+#include "svoc/route.hpp"
 #include "svoc/sortnet.hpp"
 #include "svoc/status.hpp"
 
@@ -515,23 +515,23 @@ extern "C" int svoc_fast_round_f32(const FastParams* p, hipStream_t stream) {
   if ((int64_t)p->N * p->ld * 4 >= (1ll << 31)) return -1;   // 32-bit buffer offsets
   if (p->mode != 1 && (!p->work || p->work_pairs < fast_work_pairs(p->D) || p->work_stride < fast_work_words(p->D)))
     return -1;   // pass 2 stages its outputs in the workspace
-  // default: the one-network window kernel (consensus_fast_winf.hip) where it applies; wave_hint -7
+  // default: the one-network window kernel (consensus_fast_winf.hip) where the route takes it; wave_hint -7
   // forces this two-network kernel (tests cross-check the two)
-  if (p->wave_hint != -7) {
-    const int rc = svoc_fast_round_f32_win(p, stream);
-    if (rc != -2) return rc;
-  }
-  if (p->upd_rows) return -3;   // fused transactional streaming exists in the window kernel only
+  const FastRoute r = fast_route(fast_shape(*p, kStoreF32));
   if (p->rst_saved) return -3;  // in-kernel rollback: the bf16 window kernel only
+  if (r.kernel == kFastWindow) return svoc_fast_round_f32_win(p, stream);
+  if (p->upd_rows) return -3;   // fused transactional streaming exists in the window kernel only
   int rc;
-  if (p->N <= 64) rc = launch_f32<1>(*p, stream);
-  else if (p->N <= 128) rc = launch_f32<2>(*p, stream);
-  else if (p->N <= 256) rc = launch_f32<4>(*p, stream);
-  else if (p->N <= 512) rc = launch_f32<8>(*p, stream);
-  else if (p->N <= 1024) rc = launch_f32<16>(*p, stream);
-  // N > 1024: 32 / 64 lanes per column (two / one column per wave), the same cross-lane bitonic sort
-  else if (p->N <= 2048) rc = launch_f32<32>(*p, stream);
-  else rc = launch_f32<64>(*p, stream);
+  switch (r.lane_groups) {
+    case 1: rc = launch_f32<1>(*p, stream); break;
+    case 2: rc = launch_f32<2>(*p, stream); break;
+    case 4: rc = launch_f32<4>(*p, stream); break;
+    case 8: rc = launch_f32<8>(*p, stream); break;
+    case 16: rc = launch_f32<16>(*p, stream); break;
+    // N > 1024: 32 / 64 lanes per column (two / one column per wave), the same cross-lane bitonic sort
+    case 32: rc = launch_f32<32>(*p, stream); break;
+    default: rc = launch_f32<64>(*p, stream);
+  }
   // c1 (mode 0 with c1_out): the window kernel commits it itself, this kernel stages it
   if (rc == 0 && p->mode == 0 && p->c1_out)
     rc = svoc_commit_rows(p->c1, p->c1_out, p->status, p->active, p->B, p->D, stream);

@@ -30,7 +30,7 @@
 #include <utility>
 
 #include "svoc/bufload.hpp"
-#include "svoc/launch.hpp"
+#include "svoc/route.hpp"
 #include "svoc/rankmask.hpp"
 #include "svoc/sortnet.hpp"
 #include "svoc/status.hpp"
@@ -876,48 +876,44 @@ static void launch_win(const FastParams& p, int H, hipStream_t stream) {
 
 using namespace svoc;
 
-// Returns -2 when the window kernel does not apply (no workspace, f > 32, ...): the caller falls back.
+// Returns -2 when the window kernel does not apply (route.hpp FastRoute::win_h: no workspace, f > 32, ...).
+static int launch_win_route(const FastParams& p, const FastRoute& r, hipStream_t stream) {
+  if (!p.work || !r.win_h) return -2;
+  if (p.work_pairs < fast_work_pairs(p.D) || p.work_pairs % 256 != 0 || p.work_stride < fast_work_words(p.D))
+    return -1;
+  switch (r.lane_groups) {
+    case 1: launch_win<1>(p, r.win_h, stream); break;
+    case 2: launch_win<2>(p, r.win_h, stream); break;
+    default: launch_win<4>(p, r.win_h, stream);
+  }
+  return (int)hipGetLastError();
+}
+
 extern "C" int svoc_fast_round_bf16_win(const FastParams* p, hipStream_t stream) {
   if (p->B <= 0) return 0;
-  if (!p->work || p->N < 2 || p->N > 256 || p->ld % 8 != 0 || p->D > p->ld) return -2;
-  if (p->mode == 2 && p->work_fresh) return -2;   // pass 1 ran elsewhere: no windows to read
-  if (p->n_failing < 0 || p->n_failing > 32 || p->n_failing > p->N - 2) return -2;
-  const int H = fast_win_h(p->N, p->n_failing);
-  if (H == 0) return -2;
-  if (p->work_pairs < fast_work_pairs(p->D) || p->work_pairs % 256 != 0 || p->work_stride < fast_work_words(p->D))
-    return -1;
-  if (p->N <= 64) launch_win<1>(*p, H, stream);
-  else if (p->N <= 128) launch_win<2>(*p, H, stream);
-  else launch_win<4>(*p, H, stream);
-  return (int)hipGetLastError();
+  return launch_win_route(*p, fast_route(fast_shape(*p, kStoreBf16)), stream);
 }
 
 extern "C" int svoc_fast_round_bf16_reg(const FastParams* p, hipStream_t stream);
 extern "C" int svoc_fast_round_bf16_small(const FastParams* p, hipStream_t stream);
 
-// The bf16-storage fast round: which kernel runs.
-//   small instances (N <= 16, D <= 128, whole round): several instances per wave, registers only
-//     (consensus_fast_small.hip);
-//   default: this one-network window kernel where it applies (workspace given, f <= 32, N <= 256);
+// The bf16-storage fast round: the kernel the route names (route.hpp fast_route).
+//   small instances: several instances per wave, registers only (consensus_fast_small.hip);
+//   default: this one-network window kernel where it applies;
 //   otherwise, and for wave_hint -7 (tests: the cross-check), the two-network register-streaming kernel
 //     (consensus_fast_reg.hip).
 //   c1 (mode 0 with c1_out): the window and small kernels commit it themselves; after the others,
 //   commit_rows does.
+//   -3: the launch asks for what the routed kernel cannot do (fused streaming: the fp32 window kernel only;
+//   in-kernel rollback: FastRoute::rollback).
 extern "C" int svoc_fast_round_bf16(const FastParams* p, hipStream_t stream) {
   if (p->B <= 0) return 0;
-  int rc;
-  if (p->upd_rows) return -3;   // fused transactional streaming: the fp32 window kernel only
-  if (p->wave_hint == 0 && p->mode == 0 && p->N <= 16 && p->D <= 128) {
-    if (p->rst_saved) return -3;   // in-kernel rollback: the window kernel only
-    return svoc_fast_round_bf16_small(p, stream);   // (commits c1 into c1_out itself)
-  } else {
-    if (p->wave_hint != -7) {
-      rc = svoc_fast_round_bf16_win(p, stream);
-      if (rc != -2) return rc;
-    }
-    if (p->rst_saved) return -3;
-    rc = svoc_fast_round_bf16_reg(p, stream);
-  }
+  const FastRoute r = fast_route(fast_shape(*p, kStoreBf16));
+  if (p->upd_rows || (p->rst_saved && !r.rollback)) return -3;
+  if (r.needs_work && !p->work) return -1;   // pass 2 stages its outputs in the workspace
+  if (r.kernel == kFastSmall) return svoc_fast_round_bf16_small(p, stream);   // (commits c1 into c1_out itself)
+  if (r.kernel == kFastWindow) return launch_win_route(*p, r, stream);
+  int rc = svoc_fast_round_bf16_reg(p, stream);
   if (rc == 0 && p->mode == 0 && p->c1_out)
     rc = svoc_commit_rows(p->c1, p->c1_out, p->status, p->active, p->B, p->D, stream);
   return rc;

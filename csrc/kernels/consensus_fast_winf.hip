@@ -33,7 +33,7 @@
 #include <utility>
 
 #include "svoc/bufload.hpp"
-#include "svoc/launch.hpp"
+#include "svoc/route.hpp"
 #include "svoc/slabdma.hpp"
 #include "svoc/rankmask.hpp"
 #include "svoc/sortnet.hpp"
@@ -1085,25 +1085,24 @@ static void launch_winf(const FastParams& p, int H, hipStream_t stream) {
 
 using namespace svoc;
 
-// Returns -2 when the window kernel does not apply (no workspace, f > 32, N > 256, ...): the caller
-// falls back to the two-network fp32 kernel.
+// Returns -2 when the window kernel does not apply (route.hpp FastRoute::win_h: no workspace, f > 32, N > 256,
+// ...): the caller falls back to the two-network fp32 kernel.  -3: a fused batch or a deferred commit the route
+// does not take.
 extern "C" int svoc_fast_round_f32_win(const FastParams* p, hipStream_t stream) {
   if (p->B <= 0) return 0;
-  if (!p->work || p->N < 2 || p->N > 256 || p->D > p->ld) return -2;
-  if ((int64_t)p->N * p->ld * 4 >= (1ll << 31)) return -2;
-  if (p->mode == 2 && p->work_fresh) return -2;   // pass 1 ran elsewhere: no windows to read
-  if (p->upd_rows && (p->mode != 0 || !p->constrained || p->upd_per_inst <= 0 || p->upd_per_inst > 256 ||
-                      (int64_t)p->upd_per_inst * p->D * 4 >= (1ll << 31) || (int64_t)p->ld * 4 >= (1ll << 24)))
+  FastShape s = fast_shape(*p, kStoreF32);
+  s.wave_hint = 0;   // (a direct call asks for this kernel whatever the hint)
+  const FastRoute r = fast_route(s);
+  if (!p->work || !r.win_h) return -2;
+  if (p->upd_rows && (p->upd_per_inst <= 0 || p->upd_per_inst > r.fused_max_u)) return -3;
+  if (p->pend_rows && (!p->upd_rows || !p->pend_oracle || !p->pend_status || p->upd_per_inst > r.defer_max_u))
     return -3;
-  if (p->pend_rows && (!p->upd_rows || !p->pend_oracle || !p->pend_status || p->upd_per_inst > 127 || p->D % 4 != 0))
-    return -3;
-  if (p->n_failing < 0 || p->n_failing > 32 || p->n_failing > p->N - 2) return -2;
-  const int H = fast_win_h(p->N, p->n_failing);
-  if (H == 0) return -2;
   if (p->work_pairs < fast_work_pairs(p->D) || p->work_pairs % 256 != 0 || p->work_stride < fast_work_words(p->D))
     return -1;
-  if (p->N <= 64) launch_winf<1>(*p, H, stream);
-  else if (p->N <= 128) launch_winf<2>(*p, H, stream);
-  else launch_winf<4>(*p, H, stream);
+  switch (r.lane_groups) {
+    case 1: launch_winf<1>(*p, r.win_h, stream); break;
+    case 2: launch_winf<2>(*p, r.win_h, stream); break;
+    default: launch_winf<4>(*p, r.win_h, stream);
+  }
   return (int)hipGetLastError();
 }

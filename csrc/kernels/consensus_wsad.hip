@@ -32,7 +32,7 @@
 #include <utility>
 
 #include "svoc/bufload.hpp"
-#include "svoc/launch.hpp"
+#include "svoc/route.hpp"
 #include "svoc/sortnet.hpp"
 #include "svoc/status.hpp"
 #include "svoc/wsad.hpp"
@@ -1177,8 +1177,8 @@ static int launch_wsad_c(const ExactParams& p, hipStream_t stream) {
   constexpr int WAVES = 4;
   auto k = p.val32 ? consensus_wsad_kernel<NSEG, WAVES, true, 0, CONS> : consensus_wsad_kernel<NSEG, WAVES, false, 0, CONS>;
   if constexpr (CONS) {
-    // whole constrained rounds: the one-network window path (exact_win_h: 0 = a second network)
-    const int h = p.mode == 0 && !p.legacy ? exact_win_h(p.N, p.n_failing) : 0;
+    // whole constrained rounds: the one-network window path (ExactRoute::win_h: 0 = a second network)
+    const int h = exact_route(exact_shape(p)).win_h;
     if (h == 5) k = p.val32 ? consensus_wsad_kernel<NSEG, WAVES, true, 0, true, 5> : consensus_wsad_kernel<NSEG, WAVES, false, 0, true, 5>;
     if (h == 17) k = p.val32 ? consensus_wsad_kernel<NSEG, WAVES, true, 0, true, 17> : consensus_wsad_kernel<NSEG, WAVES, false, 0, true, 17>;
     if (h != p.win_h) return -3;   // (the caller sized the stage for p.win_h)
@@ -1227,40 +1227,31 @@ using namespace svoc;
 // -2: not applicable (the caller runs the i128 kernel on every instance).
 extern "C" int svoc_exact_round_wsad(const ExactParams* p, hipStream_t stream) {
   if (p->B <= 0) return 0;
-  // lane = column: with few columns most lanes idle, and for N <= 32 the i128 kernel packs 2-8
-  // instances per wave instead (profiles/r2_exact_crossover.json: 7 x 6 140 M vs 10 M rounds/s,
-  // 16 x 16 27 M vs 10 M; but 64 x 16 already 8.3 M vs 6.0 M for this kernel)
-  if (p->N < 4 || p->N > 4096) return -2;
-  if (p->N > 256 && p->mode != 0 && !p->constrained) return -2;   // (wide groups: D-sharded halves constrained)
-  if (p->N <= 32 && p->D < p->wsad_min_d) return -2;
-  if (!p->stage || !p->fallback) return -2;
-  if ((int64_t)p->N * p->D * (p->val32 ? 4 : 8) >= (1ll << 31)) return -2;   // 32-bit buffer offsets
-  if (p->N <= 64) return launch_wsad<1>(*p, stream);
-  if (p->N <= 128) return launch_wsad<2>(*p, stream);
-  if (p->N <= 256) return launch_wsad<4>(*p, stream);
-  if (p->N <= 512) return launch_wide<8>(*p, stream);
-  if (p->N <= 1024) return launch_wide<16>(*p, stream);
-  if (p->N <= 2048) return launch_wide<32>(*p, stream);
-  return launch_wide<64>(*p, stream);
+  const ExactRoute r = exact_route(exact_shape(*p));
+  if (!r.column || !p->stage || !p->fallback) return -2;
+  switch (r.lane_groups) {
+    case 1: return launch_wsad<1>(*p, stream);
+    case 2: return launch_wsad<2>(*p, stream);
+    case 4: return launch_wsad<4>(*p, stream);
+    case 8: return launch_wide<8>(*p, stream);
+    case 16: return launch_wide<16>(*p, stream);
+    case 32: return launch_wide<32>(*p, stream);
+    default: return launch_wide<64>(*p, stream);
+  }
 }
 
-// Whether the verdict form takes the rounds of *p: the guards above (the stage aside: it has none), and whole
-// constrained non-legacy rounds of N <= 256 oracles.  ConsensusEngine._verdict_ok (svoc/engine.py) states the same
-// conditions to choose verdict waves for the exact stream: keep the two in step (where they differ the results stay
-// right -- the op takes the full-round path -- but every wave then pays a full round).
-extern "C" int svoc_exact_verdict_applies(const ExactParams* p) {
-  if (p->N < 4 || p->N > 256) return 0;
-  if (p->mode != 0 || !p->constrained || p->legacy) return 0;
-  if (p->N <= 32 && p->D < p->wsad_min_d) return 0;
-  if ((int64_t)p->N * p->D * (p->val32 ? 4 : 8) >= (1ll << 31)) return 0;   // 32-bit buffer offsets
-  return 1;
-}
+// Whether the verdict form takes the rounds of *p (route.hpp ExactRoute::verdict: the column kernel's guards, and
+// whole constrained non-legacy rounds of N <= 256 oracles).
+extern "C" int svoc_exact_verdict_applies(const ExactParams* p) { return exact_route(exact_shape(*p)).verdict; }
 
 // -2: not applicable (the caller runs the full round).
 extern "C" int svoc_exact_verdict_wsad(const ExactParams* p, hipStream_t stream) {
   if (p->B <= 0) return 0;
-  if (!p->fallback || !svoc_exact_verdict_applies(p)) return -2;
-  if (p->N <= 64) return launch_verdict<1>(*p, stream);
-  if (p->N <= 128) return launch_verdict<2>(*p, stream);
-  return launch_verdict<4>(*p, stream);
+  const ExactRoute r = exact_route(exact_shape(*p));
+  if (!p->fallback || !r.verdict) return -2;
+  switch (r.lane_groups) {
+    case 1: return launch_verdict<1>(*p, stream);
+    case 2: return launch_verdict<2>(*p, stream);
+    default: return launch_verdict<4>(*p, stream);
+  }
 }

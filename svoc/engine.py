@@ -182,7 +182,9 @@ class ConsensusEngine:
         self.wave_hint = 0
         self.rounds = 0
         self.failing_mask: Optional[torch.Tensor] = None   # [B, N] set by randomize()
-        self._work = None   # window-kernel workspace (GPU fast mode), allocated on first use
+        self._work = None   # fast kernels' workspace (GPU fast mode), allocated on first use
+        self._routes: Dict[int, tuple] = {}   # wave_hint -> svops.FastRoute (_route)
+        self._xroute = None                   # svops.ExactRoute (_verdict_ok)
         # transactional fast steps: the rows each apply_updates call overwrote, restored by the next round
         # for the instances whose round reverts (engine docstring)
         self.transactional = mode == "fast"
@@ -329,87 +331,97 @@ class ConsensusEngine:
             self._pending.restore(self.status if status is None else status, self._active)
 
     # ------------------------------------------------------------------ rounds
-    def run_round(self, only_touched: bool = True) -> None:
-        """Consensus round for every instance that is fully active (and touched, by default).
-
-        Three launches: the prologue selects the instances (n_active == N, touched), the fused
-        round kernel, and the epilogue commits consensus_active, clears touched and folds the
-        round's health counters into :attr:`metrics_fx` (integers: deterministic sums)."""
-        self.pipeline_join()
-        self._ops.round_prologue(self.n_active, self.touched, self.N, bool(only_touched), self._active)
-        mx = self.cfg.unconstrained_max_spread
+    def _round_over(self, sl: Optional[slice], only_touched: bool, then=None, **batch) -> None:
+        """The round sequence over the instances ``sl`` (views of the state; None: all): the prologue selects the
+        instances (n_active == N, touched), the round kernel runs, ``then`` (what a transactional step queues behind
+        it: a restore or a commit), the track record, and the epilogue commits consensus_active, clears touched
+        and folds the round's health counters into :attr:`metrics_fx` (integers: deterministic sums).
+        ``batch``: fast_round's optional update / rollback / pending tensors, by keyword."""
+        v = (lambda t: t) if sl is None else (lambda t: t[sl])
+        active = v(self._active)
+        self._ops.round_prologue(v(self.n_active), v(self.touched), self.N, bool(only_touched), active)
         if self.mode == "fast":
-            self._ops.fast_round(self.values, self._active, self.D, self.cfg.n_failing_oracles,
-                                 self.cfg.constrained, float(mx), self.c1, self.consensus, self.skew,
-                                 self.kurt, self.rel, self.qr, self.reliable, self.status, self.wave_hint,
-                                 0, 0, self.cfg.legacy, self.work(), self._net_fb)
-            self._restore_pending()
+            w = self.work()
+            if w is not None and sl is not None:
+                words = w.numel() // self.B
+                w = w[sl.start * words:sl.stop * words]
+            self._ops.fast_round(v(self.values), active, self.D, self.cfg.n_failing_oracles, self.cfg.constrained,
+                                 float(self.cfg.unconstrained_max_spread), v(self.c1), v(self.consensus),
+                                 v(self.skew), v(self.kurt), v(self.rel), v(self.qr), v(self.reliable),
+                                 v(self.status), self.wave_hint, 0, 0, self.cfg.legacy, w, self._net_fb, **batch)
         else:
-            self._ops.exact_round(self.values, self._active, self.cfg.n_failing_oracles, self.cfg.constrained,
-                                  self.cfg.max_spread_wsad, self.c1, self.consensus, self.skew, self.kurt,
-                                  self.rel, self.qr, self.reliable, self.status, self.cfg.legacy,
+            self._ops.exact_round(v(self.values), active, self.cfg.n_failing_oracles, self.cfg.constrained,
+                                  self.cfg.max_spread_wsad, v(self.c1), v(self.consensus), v(self.skew), v(self.kurt),
+                                  v(self.rel), v(self.qr), v(self.reliable), v(self.status), self.cfg.legacy,
                                   stats=self._xstats)
-        self._track_update()
-        self._ops.round_epilogue(self._active, self.status, self.rel, self.consensus_active, self.touched,
+        if then is not None:
+            then()
+        self._track_update(slice(None) if sl is None else sl)
+        self._ops.round_epilogue(active, v(self.status), v(self.rel), v(self.consensus_active), v(self.touched),
                                  self.metrics_fx)
+
+    def run_round(self, only_touched: bool = True) -> None:
+        """Consensus round for every instance that is fully active (and touched, by default): three launches
+        (:meth:`_round_over`), and the restore of the pending update batches where a fast round reverted."""
+        self.pipeline_join()
+        self._round_over(None, only_touched, then=self._restore_pending if self.mode == "fast" else None)
         self.rounds += 1
 
     def _run_round_range(self, b0: int, b1: int, only_touched: bool = True, restore=None, U: int = 0) -> None:
-        """run_round over instances [b0, b1) only (views of the state; fast mode); ``restore``: the
-        range's saved update batch (inst, oracle, st, saved, saved_en), rolled back where it reverted --
-        by the round kernel itself when ``U`` (updates per instance, instance-grouped) is given and the
-        kernel supports it (:meth:`_kernel_rollback_ok`), else by the restore kernel after it."""
+        """run_round over instances [b0, b1) only (fast mode); ``restore``: the range's saved update batch (inst,
+        oracle, st, saved, saved_en), rolled back where it reverted -- by the round kernel itself when ``U``
+        (updates per instance, instance-grouped) is given and the kernel supports it
+        (:meth:`_kernel_rollback_ok`), else by the restore kernel after it."""
         sl = slice(b0, b1)
-        self._ops.round_prologue(self.n_active[sl], self.touched[sl], self.N, bool(only_touched), self._active[sl])
-        w = self.work()
-        if w is not None:
-            words = w.numel() // self.B
-            w = w[b0 * words:b1 * words]
-        args = (self.values[sl], self._active[sl], self.D, self.cfg.n_failing_oracles,
-                self.cfg.constrained, float(self.cfg.unconstrained_max_spread), self.c1[sl],
-                self.consensus[sl], self.skew[sl], self.kurt[sl], self.rel[sl], self.qr[sl],
-                self.reliable[sl], self.status[sl], self.wave_hint, 0, 0, self.cfg.legacy, w, self._net_fb)
         if restore is not None and U > 0:
             _, oracle, st, saved, saved_en = restore
             self._all_active = False   # (a reverted first commit lowers n_active)
-            self._ops.fast_round(*args, None, oracle.contiguous(), st, U, saved, saved_en, self.enabled[sl],
-                                 self.n_active[sl])
+            self._round_over(sl, only_touched, upd_oracle=oracle.contiguous(), upd_status=st, upd_per_inst=U,
+                             rst_saved=saved, rst_saved_en=saved_en, rst_enabled=self.enabled[sl],
+                             rst_n_active=self.n_active[sl])
         else:
-            self._ops.fast_round(*args)
-            if restore is not None:
-                self._restore([restore])
-        self._track_update(sl)
-        self._ops.round_epilogue(self._active[sl], self.status[sl], self.rel[sl], self.consensus_active[sl],
-                                 self.touched[sl], self.metrics_fx)
+            self._round_over(sl, only_touched, then=None if restore is None else lambda: self._restore([restore]))
+
+    def _route(self) -> "svops.FastRoute":
+        """The route of this engine's GPU fast rounds (svoc.ops.fast_route: the kernel and what it supports), with
+        the engine's own workspace; asked once per ``wave_hint`` -- the rest of the shape is fixed."""
+        r = self._routes.get(self.wave_hint)
+        if r is None:
+            r = self._routes[self.wave_hint] = svops.fast_route(
+                self.storage, self.N, self.D, self.ld, self.cfg.n_failing_oracles, self.cfg.constrained,
+                self.cfg.legacy, 0, self.wave_hint, svops.WORK_CALLER)
+        return r
+
+    def _gpu_fast(self) -> bool:
+        return self.mode == "fast" and self.device.type == "cuda"
 
     def _kernel_rollback_ok(self, U: int) -> bool:
-        """Whether the round kernel itself rolls back a reverted instance's saved batch (FastParams.rst_saved):
-        the bf16 window kernel -- whole constrained rounds, 16 < N <= 256 (or D > 128: not the small-instance
-        kernel), f <= 32 with a window, U updates per instance."""
-        f = self.cfg.n_failing_oracles
+        """Whether the round kernel itself rolls back a reverted instance's saved batch (FastParams.rst_saved): the
+        route says so (the bf16 window kernel), U updates per instance, constrained rounds."""
         if os.environ.get("SVOC_KERNEL_ROLLBACK", "1") == "0":   # (A/B: the restore kernel instead)
             return False
-        return (self.mode == "fast" and self.device.type == "cuda" and self.vdtype == torch.bfloat16
-                and self.cfg.constrained and not self.cfg.legacy and self.wave_hint == 0
-                and 2 <= self.N <= 256 and (self.N > 16 or self.D > 128) and 0 <= f <= 32 and f <= self.N - 2
-                and bool(svops.fast_win_h(self.N, f)) and self.work() is not None and 0 < U)
+        return (self._gpu_fast() and bool(self._route().rollback) and 0 < U
+                # engine policy: the route also rolls back unconstrained rounds, ...
+                and self.cfg.constrained
+                # ... under every wave_hint that reaches the window kernel, ...
+                and self.wave_hint == 0
+                # ... and legacy rounds: the wider route exists but is untested, so it is not taken
+                and not self.cfg.legacy)
 
     def _fused_ok(self, inst, oracle, vals, U: int) -> bool:
-        """Whether a pipelined step can take the fused transactional path: fp32 storage on the GPU, whole
-        constrained rounds through the window kernel (N <= 256, f <= 32), at most 256 updates per instance
-        (instance-grouped batch, as step_pipelined requires), fp32 rows of exactly D columns, and every
-        instance already active (the fused round covers no activation; checked once, then tracked).
+        """Whether a pipelined step can take the fused transactional path: the route takes U updates per instance
+        (the fp32 window kernel, whole constrained rounds; instance-grouped batch, as step_pipelined requires),
+        fp32 rows of exactly D columns, and every instance already active (the fused round covers no
+        activation; checked once, then tracked).
         (bf16 storage takes the generic path: the same fusion in the bf16 window kernel measured slower than
         saving the rows, profiles/r4_c3_bf16_txn_ab.txt.)"""
         if os.environ.get("SVOC_FUSED_TXN", "1") == "0":   # (A/B: the generic path instead)
             return False
-        if not (self.mode == "fast" and self.device.type == "cuda" and self.vdtype == torch.float32
-                and self.cfg.constrained and 2 <= self.N <= 256 and 0 <= self.cfg.n_failing_oracles <= 32
-                and self.cfg.n_failing_oracles <= self.N - 2 and svops.fast_win_h(self.N, self.cfg.n_failing_oracles)
-                and 0 < U <= 256 and vals.dtype == self.vdtype and vals.dim() == 2 and vals.shape[1] == self.D
-                and oracle.dtype == torch.int64 and not self.cfg.legacy
-                # (the kernel's 32-bit batch offsets and 24-bit row-offset multiplies: svoc_fast_round_f32_win)
-                and U * self.D * 4 < (1 << 31) and self.ld * 4 < (1 << 24)):
+        if not (self._gpu_fast() and 0 < U <= self._route().fused_max_u
+                and vals.dtype == self.vdtype and vals.dim() == 2 and vals.shape[1] == self.D
+                and oracle.dtype == torch.int64
+                # engine policy: the route also fuses legacy rounds -- the wider route exists but is untested
+                and not self.cfg.legacy):
             return False
         if not getattr(self, "_all_active", False):
             if torch.cuda.is_current_stream_capturing():
@@ -429,10 +441,10 @@ class ConsensusEngine:
 
     def _defer_ok(self, U: int) -> bool:
         """Whether an open fused step may leave its commit to the next step's round (FastParams.pend_rows: the
-        piece map's pending bit and the 16-B write-back need U <= 127 and D % 4 == 0)."""
+        route's bound on U -- the piece map's pending bit, the 16-B write-back)."""
         if os.environ.get("SVOC_DEFERRED_COMMIT", "1") == "0":   # (A/B: the commit kernel after every round)
             return False
-        return 0 < U <= 127 and self.D % 4 == 0
+        return self._gpu_fast() and 0 < U <= self._route().defer_max_u
 
     def _run_round_range_fused(self, b0: int, b1: int, oracle: torch.Tensor, rows: torch.Tensor, st: torch.Tensor,
                                U: int, pend=None, commit: bool = True) -> None:
@@ -441,22 +453,10 @@ class ConsensusEngine:
         transaction status to `st`, and the commit kernel stores the accepted rows (a reverted round's rows
         never reach the state).  Deferred commit: ``commit=False`` leaves the accepted rows to the next round of
         the range, which gets them as ``pend`` = (rows, oracle, statuses) of that batch and writes them back."""
+        pend = dict(zip(("pend_rows", "pend_oracle", "pend_status"), pend)) if pend is not None else {}
         sl = slice(b0, b1)
-        self._ops.round_prologue(self.n_active[sl], self.touched[sl], self.N, False, self._active[sl])
-        w = self.work()
-        words = w.numel() // self.B
-        w = w[b0 * words:b1 * words]
-        self._ops.fast_round(self.values[sl], self._active[sl], self.D, self.cfg.n_failing_oracles,
-                             self.cfg.constrained, float(self.cfg.unconstrained_max_spread), self.c1[sl],
-                             self.consensus[sl], self.skew[sl], self.kurt[sl], self.rel[sl], self.qr[sl],
-                             self.reliable[sl], self.status[sl], self.wave_hint, 0, 0, self.cfg.legacy, w,
-                             self._net_fb, rows, oracle.contiguous(), st, U, None, None, None, None,
-                             *(pend if pend is not None else (None, None, None)))
-        if commit:
-            self._ops.commit_updates(rows, oracle, st, self.values[sl], U)
-        self._track_update(sl)
-        self._ops.round_epilogue(self._active[sl], self.status[sl], self.rel[sl], self.consensus_active[sl],
-                                 self.touched[sl], self.metrics_fx)
+        self._round_over(sl, False, upd_rows=rows, upd_oracle=oracle.contiguous(), upd_status=st, upd_per_inst=U, **pend,
+                         then=(lambda: self._ops.commit_updates(rows, oracle, st, self.values[sl], U)) if commit else None)
 
     def step_pipelined(self, inst: torch.Tensor, oracle: torch.Tensor, vals: torch.Tensor,
                        updates_per_instance: int, chunks: int = 2, overlap: bool = False) -> None:
@@ -476,9 +476,9 @@ class ConsensusEngine:
         every other engine method) joins the streams into the current stream before anything else
         touches the state.
 
-        Pending commit (open pipeline, fused fp32 path, U <= 127, D % 4 == 0; ``SVOC_DEFERRED_COMMIT=0`` turns
-        it off): the accepted rows of an open step are not stored by a commit kernel.  The next open step's
-        round of the same range reads them from the held batch and writes them to ``values`` while it streams
+        Pending commit (open pipeline, fused fp32 path, U within the route's ``defer_max_u``;
+        ``SVOC_DEFERRED_COMMIT=0`` turns it off): the accepted rows of an open step are not stored by a commit
+        kernel.  The next open step's round of the same range reads them from the held batch and writes them to ``values`` while it streams
         the instance; the last open step's rows are stored by the commit kernel at the join.  So between joins
         ``values`` may lag by one accepted batch per range -- outputs and statuses never do -- and after
         :meth:`pipeline_join` it is exact.  A step that does not match the pending one (other ``U``, other
@@ -613,13 +613,10 @@ class ConsensusEngine:
             self._pipe_held = None
 
     def work(self) -> Optional[torch.Tensor]:
-        """Workspace of the one-network window kernel (34 window keys + 8 power sums + 2 cleanup
-        list slots per column pair: 176 B per column pair and instance); None where that kernel does not run (CPU, small
-        instances, more than 32 failing oracles)."""
-        if self.mode != "fast" or self.device.type != "cuda":
+        """Workspace of the fast kernels (window keys, power sums, cleanup list and staged pass-2 outputs per
+        column: launch.hpp fast_work_words); None where the route needs none (CPU, the small-instance kernel)."""
+        if not self._gpu_fast() or not self._route().needs_work:
             return None
-        if self.vdtype == torch.bfloat16 and not svops.fast_work_applies(self.N, self.D, self.cfg.n_failing_oracles):
-            return None   # (the fp32 kernel always stages its pass-2 outputs there)
         if self._work is None:
             self._work = torch.empty(svops.fast_work_numel(self.B, self.D), dtype=torch.int32,
                                      device=self.device)
@@ -630,8 +627,7 @@ class ConsensusEngine:
         ``slab_networks`` run so far (processed rounds x full 64-column slab steps x 4 waves) and the
         ``fallbacks`` among them whose exact check failed (the full network reran for that wave)."""
         self.pipeline_join()
-        if self._net_fb is None or not svops.pruned_window_applies(self.N, self.cfg.n_failing_oracles,
-                                                                  self.cfg.constrained, self.storage):
+        if self._net_fb is None or not self._route().pruned:
             return {"slab_networks": 0, "fallbacks": 0}
         processed = int(self.metrics_fx[2].item())
         return {"slab_networks": processed * (self.D // 64) * 4, "fallbacks": int(self._net_fb.item())}
@@ -661,13 +657,10 @@ class ConsensusEngine:
 
     def _verdict_ok(self) -> bool:
         """Whether the strided exact stream judges its waves with verdict rounds and computes the outputs once
-        per step: the GPU, and the shapes and configs the verdict form of the column kernel takes (whole
-        constrained non-legacy rounds, 4 <= N <= 256, the column kernel's own guards: svoc_exact_verdict_applies).
+        per step: on the GPU, where the verdict form of the column kernel takes the engine's rounds
+        (svoc.ops.exact_route, asked once: under the exact ops' environment switches as they are then; elsewhere
+        ``exact_verdict`` runs full rounds, so every wave would pay one).
         ``SVOC_VERDICT_WAVES=0`` selects one full round per wave (A/B).
-
-        These conditions must match ``svoc_exact_verdict_applies`` (csrc/kernels/consensus_wsad.hip) and the
-        switches the binding reads (``SVOC_EXACT_I128``, ``SVOC_EXACT_WSAD_MIN_D``): where they differ the results
-        stay right, since ``exact_verdict`` then runs full rounds, but every wave pays one.
 
         Never with ``cfg.track_oracles``: the track record needs every transaction's ``reliable`` mask and
         ``qr``, which a verdict round does not compute, so a tracking engine runs one full round per wave."""
@@ -675,12 +668,12 @@ class ConsensusEngine:
             return False
         if os.environ.get("SVOC_VERDICT_WAVES", "1") == "0":
             return False
-        if os.environ.get("SVOC_EXACT_I128", "0")[:1] == "1":
+        if self.mode != "exact" or self.device.type != "cuda":
             return False
-        min_d = int(os.environ.get("SVOC_EXACT_WSAD_MIN_D", "64"))
-        return (self.mode == "exact" and self.device.type == "cuda" and self.cfg.constrained
-                and not self.cfg.legacy and 4 <= self.N <= 256 and not (self.N <= 32 and self.D < min_d)
-                and self.N * self.D * self.values.element_size() < (1 << 31))
+        if self._xroute is None:
+            self._xroute = svops.exact_route(self.N, self.D, self.values.element_size(), self.cfg.n_failing_oracles,
+                                             self.cfg.constrained, self.cfg.legacy)
+        return bool(self._xroute.verdict)
 
     def metrics(self) -> torch.Tensor:
         """[sum rel2 of committed rounds, committed, processed, reverted] as float64 (device)."""

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import os
 import threading
+from typing import NamedTuple
 
 import torch
 
@@ -60,36 +61,55 @@ def ops():
 from . import torch_ref  # noqa: E402,F401
 
 
+# ---- routes (csrc/include/svoc/route.hpp): which kernel runs a round and what it supports.  The C++ functions the
+# dispatchers switch on, asked through tensor-less ops; nothing about a kernel's limits is restated here.
+STORAGE = {"bf16": 0, "fp32": 1}              # route.hpp FastStorage
+WORK_NONE, WORK_CALLER, WORK_FRESH = 0, 1, 2  # route.hpp FastWork
+KERNEL_SMALL, KERNEL_WINDOW, KERNEL_TWO_NETWORK = 0, 1, 2   # route.hpp FastKernel
+
+
+class FastRoute(NamedTuple):
+    kernel: int        # KERNEL_*
+    lane_groups: int
+    win_h: int         # the window kernel's half-width where it applies to the shape (0: it does not)
+    needs_work: int    # the kernel needs a workspace (the binding allocates a fresh one per call without the caller's)
+    pruned: int        # the pruned window network runs
+    rollback: int      # the kernel rolls back a saved batch itself (fast_round's rst_saved)
+    fused_max_u: int   # most updates per instance the fused path takes (0: none)
+    defer_max_u: int   # ... and its deferred commit (0: none)
+
+
+class ExactRoute(NamedTuple):
+    column: int        # the column-parallel kernel applies (else the i128 kernel alone)
+    lane_groups: int   # 1 / 2 / 4, or the wide groups 8 .. 64
+    win_h: int
+    verdict: int       # the verdict form of the column kernel applies
+
+
+def fast_route(storage: str, N: int, D: int, ld: int, n_failing: int, constrained: bool, legacy: bool = False,
+               mode: int = 0, wave_hint: int = 0, work: int = WORK_CALLER) -> FastRoute:
+    """The route of a GPU fast round of this shape (route.hpp fast_route)."""
+    return FastRoute(*ops().fast_route(STORAGE[storage], N, D, ld, n_failing, bool(constrained), bool(legacy), mode,
+                                       wave_hint, work))
+
+
+def exact_route(N: int, D: int, elem_bytes: int, n_failing: int, constrained: bool, legacy: bool = False,
+                mode: int = 0) -> ExactRoute:
+    """The route of a GPU exact round of this shape (route.hpp exact_route), under the environment switches
+    ``SVOC_EXACT_I128`` / ``SVOC_EXACT_WSAD_MIN_D`` as they are set now (the op reads them, as exact_round does)."""
+    return ExactRoute(*ops().exact_route(N, D, elem_bytes, n_failing, bool(constrained), bool(legacy), mode))
+
+
 def fast_work_words(D: int) -> int:
-    """u32 words per instance of the window kernel's workspace (csrc/include/svoc/launch.hpp)."""
-    pairs = ((D + 1) // 2 + 255) // 256 * 256
-    return pairs * 2 * (2 * 17 + 4 + 1 + 3)   # fp32 window layout (the larger of the two)
+    """u32 words per instance of the fast kernels' workspace (launch.hpp fast_work_words)."""
+    return ops().fast_work_words(D)
 
 
 def fast_work_numel(B: int, D: int) -> int:
-    """Total int32 elements of the window kernel's workspace (B instances)."""
+    """Total int32 elements of the fast kernels' workspace (B instances)."""
     return B * fast_work_words(D)
-
-
-def fast_work_applies(N: int, D: int, n_failing: int) -> bool:
-    """Whether the default GPU fast round needs the workspace: every kernel but the small-instance
-    one (N <= 16 and D <= 128) keeps its window state and staged pass-2 outputs there."""
-    return N > 16 or D > 128
-
 
 
 def fast_win_h(N: int, f: int) -> int:
     """Window half-width of the one-network kernels (launch.hpp fast_win_h): 5, 17, or 0 (no window)."""
-    R = N - f
-    a = N // 2 - R // 2
-    if a + 1 <= 5 and f - a + 1 <= 5:
-        return 5
-    if a + 1 <= 17 and f - a + 1 <= 17:
-        return 17
-    return 0
-
-
-def pruned_window_applies(N: int, n_failing: int, constrained: bool, storage: str) -> bool:
-    """The fp32 window kernel's pruned network runs (N = 256, H = 17, constrained; csrc/kernels/
-    consensus_fast_winf.hip + sortnet.hpp window_group_pruned) -- on every full 64-column slab step."""
-    return storage == "fp32" and constrained and N == 256 and 0 <= n_failing <= 32 and fast_win_h(N, n_failing) == 17
+    return ops().fast_win_h(N, f)
