@@ -115,9 +115,7 @@ class _PendingBatches:
         e = self.e
         e._all_active = False   # (a reverted first commit lowers n_active: the fused path re-checks)
         if self.dense is None:
-            for inst, oracle, st, saved, saved_en in reversed(self.entries):
-                e._ops.restore_updates(e.values, e.enabled, e.n_active, inst, oracle, st, saved, saved_en,
-                                       status, active)
+            e._restore(self.entries, status, active)
         else:
             rev = (active != 0) & (status != int(Status.OK))
             pv, pe, pn = self.dense
@@ -199,6 +197,20 @@ class ConsensusEngine:
         self._vstats = torch.zeros(3, dtype=torch.int32, device=dev) if (mode == "exact" and dev.type == "cuda") else None
         self._pending = _PendingBatches(self)
         self._save_bufs: Dict[tuple, tuple] = {}
+        self._all_active = False      # every instance known fully active (_fused_ok: checked once, then tracked)
+        # step_pipelined: its streams, whether an overlap=True step is open, the batches the side streams still
+        # read, the pending commit, and the fused path's latest update statuses
+        self._pipe_streams = None
+        self._pipe_open = False
+        self._pipe_held = None
+        self._defer = None
+        self._last_st = None
+        # svoc.parallel.dshard: a deferred round (active, status, qr, c1), its saved update batches, its
+        # (group, world) and the shadow outputs
+        self._dshard_pending = None
+        self._dshard_pending_rows = None
+        self._dshard_ctx = None
+        self._dshard_shadow = None
         # health counters folded in by every round's epilogue: [rel2 sum (2^-32 units fast / wsad
         # exact), committed, processed, reverted]
         self.metrics_fx = torch.zeros(4, dtype=torch.int64, device=dev)
@@ -274,24 +286,29 @@ class ConsensusEngine:
             return v.to(self.vdtype).contiguous()
         return vals.to(self.device, self.vdtype).contiguous()
 
+    def _batch(self, inst, oracle, vals):
+        """A caller's batch as the kernels dereference it: flat contiguous int64 ids and the rows in the storage
+        dtype, all on the state's device."""
+        inst = torch.as_tensor(inst, dtype=torch.int64, device=self.device).reshape(-1).contiguous()
+        oracle = torch.as_tensor(oracle, dtype=torch.int64, device=self.device).reshape(-1).contiguous()
+        return inst, oracle, self._as_storage(torch.as_tensor(vals))
+
     def apply_updates(self, inst: torch.Tensor, oracle: torch.Tensor, vals: torch.Tensor,
                       unique: bool = False, _joined: bool = False, save=None) -> torch.Tensor:
         """Store a batch of predictions (no consensus). Returns the per-update status [U] (device).
 
         ``unique=True``: the caller guarantees distinct (instance, oracle) pairs in the batch, so the GPU
         validates and stores in one pass (no last-writer resolution)."""
-        inst = torch.as_tensor(inst, dtype=torch.int64, device=self.device).contiguous()
-        oracle = torch.as_tensor(oracle, dtype=torch.int64, device=self.device).contiguous()
         if not _joined:
             # (streams only: a pending D-shard round's commit writes outputs, not the stored rows, and
             # its pass 2 has already read them -- updates may land before it)
             self._join_streams()
-            if self.transactional and getattr(self, "_dshard_pending", None) is not None:
+            if self.transactional and self._dshard_pending is not None:
                 # ... unless the pending round's reverted instances must roll their rows back: its verdict
                 # (one status all-reduce) and the restore come first, then this batch lands on the
                 # restored rows (svoc.parallel.dshard, deferred rounds)
                 self.pipeline_join()
-        vals = self._as_storage(torch.as_tensor(vals))
+        inst, oracle, vals = self._batch(inst, oracle, vals)
         if vals.dim() != 2 or vals.shape[1] != self.D:
             raise ValueError(f"predictions must be [U, {self.D}]")
         saved = saved_en = None
@@ -318,13 +335,12 @@ class ConsensusEngine:
             self._save_bufs[key] = buf
         return buf[0][:U], buf[1][:U], buf[2][:U]
 
-    def _restore(self, entries, status=None) -> None:
-        """Roll back the saved updates of the instances whose round ran and reverted (latest batch first)."""
-        status = self.status if status is None else status
-        self._all_active = False   # (a reverted first commit lowers n_active: the fused path re-checks)
+    def _restore(self, entries, status: torch.Tensor, active: torch.Tensor) -> None:
+        """Roll back the saved update batches (inst, oracle, st, saved, saved_en) of the instances whose round ran
+        (``active``) and reverted (``status``), latest batch first."""
         for inst, oracle, st, saved, saved_en in reversed(entries):
             self._ops.restore_updates(self.values, self.enabled, self.n_active, inst, oracle, st, saved, saved_en,
-                                      status, self._active)
+                                      status, active)
 
     def _restore_pending(self, status=None) -> None:
         if self._pending:
@@ -373,14 +389,17 @@ class ConsensusEngine:
         (updates per instance, instance-grouped) is given and the kernel supports it
         (:meth:`_kernel_rollback_ok`), else by the restore kernel after it."""
         sl = slice(b0, b1)
-        if restore is not None and U > 0:
+        if restore is None:
+            self._round_over(sl, only_touched)
+            return
+        self._all_active = False   # (a reverted first commit lowers n_active: the fused path re-checks)
+        if U > 0:
             _, oracle, st, saved, saved_en = restore
-            self._all_active = False   # (a reverted first commit lowers n_active)
             self._round_over(sl, only_touched, upd_oracle=oracle.contiguous(), upd_status=st, upd_per_inst=U,
                              rst_saved=saved, rst_saved_en=saved_en, rst_enabled=self.enabled[sl],
                              rst_n_active=self.n_active[sl])
         else:
-            self._round_over(sl, only_touched, then=None if restore is None else lambda: self._restore([restore]))
+            self._round_over(sl, only_touched, then=lambda: self._restore([restore], self.status, self._active))
 
     def _route(self) -> "svops.FastRoute":
         """The route of this engine's GPU fast rounds (svoc.ops.fast_route: the kernel and what it supports), with
@@ -423,7 +442,7 @@ class ConsensusEngine:
                 # engine policy: the route also fuses legacy rounds -- the wider route exists but is untested
                 and not self.cfg.legacy):
             return False
-        if not getattr(self, "_all_active", False):
+        if not self._all_active:
             if torch.cuda.is_current_stream_capturing():
                 return False
             self._all_active = bool((self.n_active == self.N).all())
@@ -486,9 +505,7 @@ class ConsensusEngine:
         U = int(updates_per_instance)
         # the batch goes to kernels that dereference it directly (the fused round, the commit and restore
         # kernels): indices as int64 and rows in the storage dtype, all on the state's device
-        inst = torch.as_tensor(inst, dtype=torch.int64, device=self.device).reshape(-1).contiguous()
-        oracle = torch.as_tensor(oracle, dtype=torch.int64, device=self.device).reshape(-1).contiguous()
-        vals = self._as_storage(torch.as_tensor(vals))
+        inst, oracle, vals = self._batch(inst, oracle, vals)
         # (a lone apply_updates before this step is still awaiting its round: one round must cover both)
         if self.mode != "fast" or self.device.type != "cuda" or chunks <= 1 or self._pending:
             self.pipeline_join()
@@ -498,7 +515,7 @@ class ConsensusEngine:
         if inst.numel() != self.B * U:
             raise ValueError("step_pipelined: expects updates_per_instance updates for every instance")
         cur = torch.cuda.current_stream(self.device)
-        if getattr(self, "_pipe_streams", None) is None or len(self._pipe_streams) != chunks + 1:
+        if self._pipe_streams is None or len(self._pipe_streams) != chunks + 1:
             self.pipeline_join()
             self._pipe_streams = [torch.cuda.Stream(self.device) for _ in range(chunks + 1)]
         su, sc = self._pipe_streams[0], self._pipe_streams[1:]
@@ -510,7 +527,7 @@ class ConsensusEngine:
         kroll = self.transactional and not fused and self._kernel_rollback_ok(U)
         # pending commit: this step's accepted rows wait for the next step's round (docstring)
         defer = fused and overlap and self._defer_ok(U)
-        pend = getattr(self, "_defer", None)
+        pend = self._defer
         if pend is not None and not (defer and pend["U"] == U and pend["ranges"] == ranges):
             self.pipeline_join()   # flushes the pending batch
             pend = None
@@ -548,7 +565,7 @@ class ConsensusEngine:
             # queues behind this round on the same stream: no cross-stream waits).  The streams start
             # staggered by one update (sc[k] waits for range k-1's update once, after a join), so each
             # range's update runs beside another range's round, also across steps.
-            fresh = not getattr(self, "_pipe_open", False)
+            fresh = not self._pipe_open
             for k, (b0, b1) in enumerate(ranges):
                 sc[k].wait_stream(cur)
                 if fresh and k > 0:
@@ -561,9 +578,7 @@ class ConsensusEngine:
             # the side streams still read the caller's batch after this returns: hold it until the join
             # (after which the current stream is ordered behind every read, so the caching allocator may
             # hand its blocks out again)
-            held = getattr(self, "_pipe_held", None) or []
-            held.append((inst, oracle, vals))
-            self._pipe_held = held
+            self._pipe_held = (self._pipe_held or []) + [(inst, oracle, vals)]
             if defer:
                 self._defer = {"U": U, "ranges": ranges, "rows": vals, "oracle": oracle, "st": st_all,
                                "slot": 1 - pend["slot"] if pend is not None else 0}
@@ -588,14 +603,14 @@ class ConsensusEngine:
         state (getters, metrics, checkpoints, the next update) goes through here.  With a D-shard round
         pending this is a collective (one status all-reduce): every rank of the shard group must read."""
         self._join_streams()
-        if getattr(self, "_dshard_pending", None) is not None:
+        if self._dshard_pending is not None:
             from .parallel.dshard import flush_sharded
             group, world = self._dshard_ctx
             flush_sharded(self, group=group, world=world)
 
     def _join_streams(self) -> None:
-        if getattr(self, "_pipe_open", False):
-            pend = getattr(self, "_defer", None)
+        if self._pipe_open:
+            pend = self._defer
             if pend is not None:
                 # the pending commit's flush: the last open step's accepted rows, by the commit kernel on each
                 # range's stream (behind its round), before the held batch is released
@@ -746,14 +761,12 @@ class ConsensusEngine:
         """Sequential per-update transactions (contract.cairo:588-603: update_prediction stores the row,
         then the full consensus round; a round that fails reverts the whole transaction), replayed as
         waves: wave k applies the k-th update of every instance at once -- instances are independent,
-        so this is the per-instance sequential order.  Everything stays on the device: per wave one
-        gather of the old rows, the batched store, the round over the touched instances and a masked
-        restore for the transactions whose round failed.
-        ``commit=False`` (:meth:`preview_updates`): the rounds are verdicts into scratch tensors with no
-        epilogue, and the accepted rows are put back after the last wave."""
-        inst = torch.as_tensor(inst, dtype=torch.int64, device=self.device).reshape(-1)
-        oracle = torch.as_tensor(oracle, dtype=torch.int64, device=self.device).reshape(-1)
-        vals = self._as_storage(torch.as_tensor(vals))
+        so this is the per-instance sequential order.  This function normalises the batch, checks the
+        strided layout and builds the waves -- (inst_k, oracle_k, rows_k, status_k), contiguous, at most one
+        update per instance; :meth:`_waves` runs them, on both devices and for both groupings.
+        ``commit=False`` (:meth:`preview_updates`): nothing is committed, and every stored row is put back
+        after the last wave (:meth:`_undo_waves`)."""
+        inst, oracle, vals = self._batch(inst, oracle, vals)
         U = inst.numel()
         out = torch.full((U,), int(Status.NOT_ORACLE), dtype=torch.int32, device=self.device)
         if U == 0:
@@ -772,139 +785,98 @@ class ConsensusEngine:
                 lay = inst == torch.arange(U, device=self.device) // K
                 if not bool((lay | ~okl).all()):
                     K = 0
-            if K and self.device.type == "cuda":
-                return self._exact_transactions_k(inst, oracle, vals, K, out, commit)
-            waves = [torch.arange(k, U, K, device=self.device) for k in range(K)]
+        if K:
+            n = U // K
+            iw = inst.view(n, K).t().contiguous()             # [K, n]: wave k = the k-th update of every instance
+            ow = oracle.view(n, K).t().contiguous()
+            vw = vals.reshape(n, K, -1).transpose(0, 1).contiguous()
+            sw = torch.empty(K, n, dtype=torch.int32, device=self.device)
+            waves = [(iw[k], ow[k], vw[k], sw[k]) for k in range(K)]
         else:
             order, bounds = self._transaction_waves(inst, oracle)
-            waves = [order[bounds[k]:bounds[k + 1]] for k in range(len(bounds) - 1)]
-            if bounds[-1] < U:   # unknown instance / oracle: status only (interval check first), no store
-                bad = order[bounds[-1]:]
+            order, bad = order[:bounds[-1]], order[bounds[-1]:]
+            sw = torch.empty(bounds[-1], dtype=torch.int32, device=self.device)
+            waves = []
+            for lo, hi in zip(bounds, bounds[1:]):
+                sel = order[lo:hi]
+                waves.append((inst[sel], oracle[sel], vals[sel], sw[lo:hi]))
+            if bad.numel():   # unknown instance / oracle: status only (interval check first), no store
                 out[bad] = self.apply_updates(inst[bad], oracle[bad], vals[bad])
+        # verdict waves: the strided layout only, committing (the general grouping keeps full rounds)
+        verdict = bool(K) and commit and self._verdict_ok()
+        touched0 = None if commit else self.touched.clone()
+        saves = self._waves(waves, commit, verdict)
+        if K:
+            out.copy_(sw.t().reshape(-1))
+        else:
+            out[order] = sw
         if not commit:
-            touched0 = self.touched.clone()
-            p_active, p_rel, p_status = self._active.clone(), self.rel.clone(), self.status.clone()
-            undo = []
-        for sel in waves:
-            bi, oi = inst[sel], oracle[sel]
-            if K:
-                # out-of-range entries (status NOT_ORACLE, never applied) point their no-op gathers and
-                # write-backs at their own layout slot (instance sel // K): with one entry per instance
-                # per wave they cannot collide with another entry's restore.  (The general path drops
-                # them in _transaction_waves.)
-                okw = (bi >= 0) & (bi < self.B) & (oi >= 0) & (oi < self.N)
-                bi_c = torch.where(okw, bi, sel // K)
-                oi_c = torch.where(okw, oi, torch.zeros_like(oi))
-            else:
-                okw, bi_c, oi_c = None, bi, oi
-            old_rows = self.values[bi_c, oi_c].clone()
-            old_en = self.enabled[bi_c, oi_c].clone()
-            old_na = self.n_active[bi_c].clone()
-            self.touched.zero_()
-            st_u = self.apply_updates(bi, oi, vals[sel])
-            if commit:
-                self.run_round(only_touched=True)    # outputs are only written when a round succeeds
-                st_b = self.status[bi_c]
-            else:
-                self._verdict_round(p_active, p_rel, p_status, count=False)
-                st_b = p_status[bi_c]
-                undo.append((bi_c, oi_c, old_rows, old_en, old_na))
-            full = self.n_active[bi_c] == self.N
-            tx = torch.where(st_u != 0, st_u,
-                             torch.where(full, st_b, torch.full_like(st_b, int(Status.NOT_ACTIVE))))
-            revert = (st_u == 0) & full & (st_b != int(Status.OK))
-            if okw is not None:
-                revert = revert & okw
-            # roll back reverted transactions (contract semantics: the whole tx disappears)
-            self.values[bi_c, oi_c] = torch.where(revert[:, None], old_rows, self.values[bi_c, oi_c])
-            self.enabled[bi_c, oi_c] = torch.where(revert, old_en, self.enabled[bi_c, oi_c])
-            self.n_active[bi_c] = torch.where(revert, old_na, self.n_active[bi_c])
-            out[sel] = tx
-        if not commit:
-            # the accepted (and the stored, not yet active) rows go back, newest wave first; a row its wave did
-            # not change gets the value it has
-            for bi_c, oi_c, old_rows, old_en, old_na in reversed(undo):
-                self.values[bi_c, oi_c] = old_rows
-                self.enabled[bi_c, oi_c] = old_en
-                self.n_active[bi_c] = old_na
+            self._undo_waves(waves, saves)
             self.touched.copy_(touched0)
         return out
 
-    def _exact_transactions_k(self, inst, oracle, vals, K: int, out: torch.Tensor, commit: bool = True) -> torch.Tensor:
-        """_exact_transactions for the b * K + k layout on the GPU, with the transaction bookkeeping in the update
-        and restore kernels: per wave the update kernel validates, saves the overwritten row / ``enabled`` flag
-        and stores (one launch), the round runs, and the restore kernel rolls back the transactions whose round
-        reverted and gives every applied update its transaction status -- the round's code, NOT_ACTIVE where the
-        instance is not fully active (the update stays stored), OK otherwise.  The per-wave gathers, compares,
-        ``where`` selects and scatters of the general path (~20 small kernels, ~10 % of a c3 wave) go away; the
-        batch is reordered wave-major once.
+    def _waves(self, waves, commit: bool, verdict: bool):
+        """Run transaction waves (inst, oracle, rows, status out; at most one update per instance each), with the
+        transaction bookkeeping in the update and restore ops: per wave the update validates, saves the
+        overwritten row / ``enabled`` flag and stores (one launch), a round judges the touched instances, and
+        the restore rolls back the transactions whose round reverted and gives every applied update its
+        transaction status -- the round's code, NOT_ACTIVE where the instance is not fully active (the update
+        stays stored), OK otherwise.  Ids out of range never reach a row: both ops bound-check them.
 
-        Verdict waves (:meth:`_verdict_ok`): an accepted round overwrites every output in full, so of a step's
-        rounds only the last accepted one of an instance is visible in the outputs -- the waves need the verdict
-        alone (``exact_verdict``: status, rel for the epilogue's counters), and one full round after the last
-        wave, over the instances that accepted any, computes the outputs from the rows that round left: later
+        The judge is a full round (``run_round``), or with ``verdict`` (:meth:`_verdict_ok`) a verdict round and
+        the epilogue: an accepted round overwrites every output in full, so of a step's rounds only the last
+        accepted one of an instance is visible in the outputs -- the waves need the verdict alone
+        (``exact_verdict``: status, rel for the epilogue's counters), and one full round after the last wave,
+        over the instances that accepted any, computes the outputs from the rows that round left: later
         transactions of the instance reverted or were rejected, so the rows are the ones it saw.
 
-        ``commit=False`` (:meth:`preview_updates`): verdicts into scratch tensors, no epilogue, every wave keeps
-        its saved rows, and after the last wave they all go back, newest wave first."""
-        n = inst.numel() // K
-        iw = inst.view(n, K).t().contiguous()                 # [K, n]: wave k = the k-th update of every instance
-        ow = oracle.view(n, K).t().contiguous()
-        vw = vals.reshape(n, K, -1).transpose(0, 1).contiguous()
-        sw = torch.empty(K, n, dtype=torch.int32, device=self.device)
+        ``commit=False`` (:meth:`preview_updates`): verdicts into scratch tensors, no epilogue, no counters, and
+        every wave keeps its own saved rows; returns them, (saved, saved_en) per wave, for :meth:`_undo_waves`."""
+        active, rel, status = self._active, self.rel, self.status
         if not commit:
-            return self._preview_k(iw, ow, vw, sw, out)
-        sv, sen, _ = self._save_buffer(("exact_tx",), n)
-        verdict = self._verdict_ok()
-        mx = self.cfg.max_spread_wsad
+            active, rel, status = active.clone(), rel.clone(), status.clone()
         if verdict:
             accepted = torch.zeros(self.B, dtype=torch.uint8, device=self.device)   # a wave ran and came out OK
-        for k in range(K):
+        saves = []
+        for inst, oracle, rows, st in waves:
+            n = inst.numel()
+            if commit:   # (a general step's first wave is its largest: the buffer does not regrow within a step)
+                saved, saved_en, _ = self._save_buffer(("exact_tx",), n)
+            else:
+                saved = torch.empty(n, self.D, dtype=self.vdtype, device=self.device)
+                saved_en = torch.empty(n, dtype=torch.uint8, device=self.device)
+                saves.append((saved, saved_en))
             self.touched.zero_()
-            self.apply_updates(iw[k], ow[k], vw[k], unique=True, save=(sv, sen, sw[k]))
-            if verdict:
-                self._verdict_round(self._active, self.rel, self.status, count=True)
-                self._ops.round_epilogue(self._active, self.status, self.rel, self.consensus_active, self.touched,
-                                         self.metrics_fx)
-                accepted |= torch.where(self.status == int(Status.OK), self._active, 0)
+            self.apply_updates(inst, oracle, rows, unique=True, save=(saved, saved_en, st))
+            if not commit:
+                self._verdict_round(active, rel, status, count=False)
+            elif verdict:
+                self._verdict_round(active, rel, status, count=True)
+                self._ops.round_epilogue(active, status, rel, self.consensus_active, self.touched, self.metrics_fx)
+                accepted |= torch.where(status == int(Status.OK), active, 0)
                 self.rounds += 1
             else:
                 self.run_round(only_touched=True)             # outputs are only written when a round succeeds
-            self._ops.restore_updates(self.values, self.enabled, self.n_active, iw[k], ow[k], sw[k], sv, sen,
-                                      self.status, self._active, int(Status.NOT_ACTIVE))
+            self._ops.restore_updates(self.values, self.enabled, self.n_active, inst, oracle, st, saved, saved_en,
+                                      status, active, int(Status.NOT_ACTIVE))
         if verdict:
             # the outputs, once: the round of each instance's last accepted transaction
             final = torch.zeros_like(self.status)
-            self._ops.exact_round(self.values, accepted, self.cfg.n_failing_oracles, self.cfg.constrained, mx,
-                                  self.c1, self.consensus, self.skew, self.kurt, self.rel, self.qr, self.reliable,
-                                  final, self.cfg.legacy)
+            self._ops.exact_round(self.values, accepted, self.cfg.n_failing_oracles, self.cfg.constrained,
+                                  self.cfg.max_spread_wsad, self.c1, self.consensus, self.skew, self.kurt, self.rel,
+                                  self.qr, self.reliable, final, self.cfg.legacy)
             self._vstats[2:3] += ((accepted != 0) & (final != int(Status.OK))).sum().to(torch.int32)
-        out.copy_(sw.t().reshape(-1))
-        return out
+        return saves
 
-    def _preview_k(self, iw, ow, vw, sw, out: torch.Tensor) -> torch.Tensor:
-        """The waves of :meth:`_exact_transactions_k` without committing anything (preview_updates)."""
-        K, n = iw.shape
-        sv = torch.empty(K, n, self.D, dtype=self.vdtype, device=self.device)
-        sen = torch.empty(K, n, dtype=torch.uint8, device=self.device)
-        touched0 = self.touched.clone()
-        active, rel, status = self._active.clone(), self.rel.clone(), self.status.clone()
-        for k in range(K):
-            self.touched.zero_()
-            self.apply_updates(iw[k], ow[k], vw[k], unique=True, save=(sv[k], sen[k], sw[k]))
-            self._verdict_round(active, rel, status, count=False)
-            self._ops.restore_updates(self.values, self.enabled, self.n_active, iw[k], ow[k], sw[k], sv[k], sen[k],
-                                      status, active, int(Status.NOT_ACTIVE))
-        out.copy_(sw.t().reshape(-1))
-        # what is still stored (accepted, or stored into a not yet active instance) goes back, newest wave first
-        status.fill_(int(Status.DIV_BY_ZERO))   # (any revert code: restore_updates rolls back where it is not OK)
-        active.fill_(1)
-        for k in reversed(range(K)):
-            stored = torch.where(sw[k] == int(Status.NOT_ACTIVE), 0, sw[k])
-            self._ops.restore_updates(self.values, self.enabled, self.n_active, iw[k], ow[k], stored, sv[k], sen[k],
+    def _undo_waves(self, waves, saves) -> None:
+        """After a preview's last wave: what is still stored (accepted, or stored into a not yet active instance)
+        goes back, newest wave first."""
+        status = torch.full_like(self.status, int(Status.DIV_BY_ZERO))   # (any revert code: rolled back where not OK)
+        active = torch.ones_like(self._active)
+        for (inst, oracle, _, st), (saved, saved_en) in zip(reversed(waves), reversed(saves)):
+            stored = torch.where(st == int(Status.NOT_ACTIVE), 0, st)
+            self._ops.restore_updates(self.values, self.enabled, self.n_active, inst, oracle, stored, saved, saved_en,
                                       status, active)
-        self.touched.copy_(touched0)
-        return out
 
     # ------------------------------------------------------------------ synthetic data
     def randomize(self, seed: int = 0, a: float = 20.0, failing_low: float = 0.0) -> None:

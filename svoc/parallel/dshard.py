@@ -101,17 +101,17 @@ def run_round_sharded(engine, d_global: int, group=None, world: int = 1, defer: 
     instances' ``touched`` flags are cleared at once (the epilogue clears them anyway), so the next
     round's selection is unchanged."""
     e = engine
-    sh = getattr(e, "_dshard_shadow", None)
+    sh = e._dshard_shadow
     if sh is None:
         sh = e._dshard_shadow = _Shadow(e)
     rank = dist.get_rank(group) if world > 1 else 0
-    if getattr(e, "_dshard_pending", None) is not None and getattr(e, "_dshard_pending_rows", None):
+    if e._dshard_pending is not None and e._dshard_pending_rows:
         # a deferred transactional round still holds saved rows: its verdict and restore come before this
         # round's pass 1 reads the rows (an instance selected again -- e.g. by touched.fill_(1) -- would
         # otherwise compute from rows that are rolled back right after; ADVICE r5).  Without saved rows
         # the verdict keeps riding in this round's packed buffer.
         flush_sharded(e, group, world)
-    pend = getattr(e, "_dshard_pending", None)
+    pend = e._dshard_pending
     e._ops.round_prologue(e.n_active, e.touched, e.N, True, e._active)
     lg = e.cfg.legacy
     if e.mode == "fast":
@@ -179,7 +179,7 @@ def run_round_sharded(engine, d_global: int, group=None, world: int = 1, defer: 
 def flush_sharded(engine, group=None, world: int = 1) -> None:
     """Commit a deferred sharded round (one status MAX all-reduce); no-op when none is pending."""
     e = engine
-    pend = getattr(e, "_dshard_pending", None)
+    pend = e._dshard_pending
     if pend is None:
         return
     st = pend[1].clone()
@@ -187,7 +187,7 @@ def flush_sharded(engine, group=None, world: int = 1) -> None:
         dist.all_reduce(st, op=dist.ReduceOp.MAX, group=group)
     _commit(e, e._dshard_shadow, pend[0], st, pend[2], pend[3])
     e.status.copy_(st)
-    rows = getattr(e, "_dshard_pending_rows", None)
+    rows = e._dshard_pending_rows
     if rows:   # every rank rolls back its column slice of the reverted instances' update batches
         rows.restore(st, pend[0])
     e._dshard_pending_rows = None

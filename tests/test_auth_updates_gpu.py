@@ -78,8 +78,8 @@ def test_exact_stream_matches_cpu_service_and_reference():
     contracts, want = stream.replay_reference()
     cpu, gpu, gpu_general = ac.service("cpu"), ac.service(DEV), ac.service(DEV)
     st_cpu = ac.run_exact_stream(cpu, stream)
-    st_gpu = ac.run_exact_stream(gpu, stream)                         # phase 4: _exact_transactions_k
-    st_gen = ac.run_exact_stream(gpu_general, stream, strided=False)  # phase 4: the general waves
+    st_gpu = ac.run_exact_stream(gpu, stream)                         # phase 4: strided waves (verdict rounds)
+    st_gen = ac.run_exact_stream(gpu_general, stream, strided=False)  # phase 4: the general grouping's waves
     assert st_gpu == want and st_cpu == want and st_gen == want
     assert Status.NOT_ORACLE in want["phase4"] and Status.INTERVAL_INPUT in want["phase4"]
     for svc in (gpu, gpu_general):
