@@ -15,7 +15,8 @@ from svoc.status import Status
 pytestmark = pytest.mark.gpu
 
 B, CHUNKS = 6, 2
-SHAPES = [(256, 128, 32, 64), (200, 300, 20, 50), (64, 700, 8, 16)]   # N, D, f, U: one per lane-group form
+# N, D, f, U: lane groups 4, 4 (padded N), 1 and 2 (the half-widths and the rest: test_fused_model_gpu.py)
+SHAPES = [(256, 128, 32, 64), (200, 300, 20, 50), (64, 700, 8, 16), (128, 132, 8, 32)]
 KEYS = ("values", "status", "enabled", "n_active", "c1", "consensus", "rel", "reliable", "skew", "kurt", "qr")
 ZV, OK, IV, NO = (int(Status.ZERO_VARIANCE), int(Status.OK), int(Status.INTERVAL_INPUT), int(Status.NOT_ORACLE))
 
