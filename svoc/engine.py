@@ -424,7 +424,8 @@ class ConsensusEngine:
                 and self.cfg.constrained
                 # ... under every wave_hint that reaches the window kernel, ...
                 and self.wave_hint == 0
-                # ... and legacy rounds: the wider route exists but is untested, so it is not taken
+                # ... and legacy rounds.  tests/test_txn_model_gpu.py pins the unconstrained and the legacy roll-back to
+                # a model at the op level (hint 0); the engine has not been measured on the wider route: not taken
                 and not self.cfg.legacy)
 
     def _fused_ok(self, inst, oracle, vals, U: int) -> bool:
@@ -439,7 +440,8 @@ class ConsensusEngine:
         if not (self._gpu_fast() and 0 < U <= self._route().fused_max_u
                 and vals.dtype == self.vdtype and vals.dim() == 2 and vals.shape[1] == self.D
                 and oracle.dtype == torch.int64
-                # engine policy: the route also fuses legacy rounds -- the wider route exists but is untested
+                # engine policy: the route also fuses legacy rounds; legacy batches take the generic path instead (its
+                # roll-back is pinned for legacy rounds by tests/test_txn_model_gpu.py), the fused legacy form is not
                 and not self.cfg.legacy):
             return False
         if not self._all_active:

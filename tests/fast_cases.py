@@ -115,9 +115,10 @@ def _smooth_median(col_sorted, count):
     return 0.5 * (col_sorted[m - 1] + col_sorted[m])
 
 
-def ref64(x, f, constrained, max_spread):
+def ref64(x, f, constrained, max_spread, legacy=False):
     """One fast round per instance in fp64.  x: [B, N, D] of any float dtype.  Returns fp64 tensors
-    (reliable: bool)."""
+    (reliable: bool).  legacy: the obsolete contracts' round (svoc/reference.py consensus_round): the
+    constrained reliability without the / D, skewness and kurtosis zero."""
     x = x.double()
     B, N, D = x.shape
     R = N - f
@@ -131,7 +132,7 @@ def ref64(x, f, constrained, max_spread):
 
     def rel_of(mean_qr):
         if constrained:
-            return 1.0 - 2.0 * math.sqrt(mean_qr / D)
+            return 1.0 - 2.0 * math.sqrt(mean_qr / (1 if legacy else D))
         return 1.0 - min(math.sqrt(mean_qr), max_spread) / max_spread
 
     for b in range(B):
@@ -159,6 +160,8 @@ def ref64(x, f, constrained, max_spread):
         skew[b] = torch.where(safe, z3 * n / ((n - 1) * (n - 2)), torch.zeros_like(z3))
         kurt[b] = torch.where(safe, (z4 * n * (n + 1) / (n - 1) - 3 * (n - 1) ** 2) / ((n - 2) * (n - 3)),
                               torch.zeros_like(z4))
+        if legacy:
+            skew[b], kurt[b] = 0.0, 0.0
     return dict(c1=c1, qr=qr, reliable=reliable, consensus=cons, rel=rel, skew=skew, kurt=kurt)
 
 
