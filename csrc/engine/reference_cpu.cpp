@@ -6,6 +6,7 @@
 // sort.cairo (tie rule), signed_decimal.cairo (fixed point).  The evaluation order matches
 // svoc/reference.py so the first-error status codes agree.
 #include "engine.hpp"
+#include "svoc/verdict.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -200,7 +201,7 @@ int fast_round_one(const float* X, int64_t N, int64_t D, int64_t n_failing, bool
   if (N < 2) return ST_INDEX_OOB;
   std::vector<float> col(N);
   const int64_t m = N / 2;
-  const double rd = legacy ? 1.0 : (double)(rel_dim > 0 ? rel_dim : D);
+  const double rd = rel_divisor<double>(legacy, rel_dim, D);
   for (int64_t d = 0; d < D && mode != 2; ++d) {
     for (int64_t i = 0; i < N; ++i) col[i] = X[i * D + d];
     std::nth_element(col.begin(), col.begin() + m, col.end());
@@ -221,12 +222,6 @@ int fast_round_one(const float* X, int64_t N, int64_t D, int64_t n_failing, bool
     sum_qr += o.qr[i];
   }
   if (mode == 1) return ST_OK;
-  auto rel_of = [&](double mean_qr) -> float {
-    return constrained ? (float)(1.0 - 2.0 * std::sqrt(mean_qr / rd))
-                       : (float)(1.0 - std::min((double)max_spread, std::sqrt(mean_qr)) / (double)max_spread);
-  };
-  float rel1 = rel_of(sum_qr / (double)N);
-  if (!(rel1 >= 0.f && rel1 <= 1.f)) return ST_RELIABILITY_INTERVAL;
   std::vector<int64_t> order(N);
   std::iota(order.begin(), order.end(), 0);
   std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
@@ -234,13 +229,14 @@ int fast_round_one(const float* X, int64_t N, int64_t D, int64_t n_failing, bool
   });
   const int64_t R = N - n_failing;
   for (int64_t r = 0; r < N; ++r) o.reliable[order[r]] = r < R ? 1 : 0;
-  if (R < 2) return R == 0 ? ST_USIZE_UNDERFLOW : ST_INDEX_OOB;
   double sum_qr2 = 0.0;
   for (int64_t i = 0; i < N; ++i)
     if (o.reliable[i]) sum_qr2 += o.qr[i];
-  float rel2 = rel_of(sum_qr2 / (double)R);
-  if (!(rel2 >= 0.f && rel2 <= 1.f)) return ST_RELIABILITY_INTERVAL;
-  if (R < 4 && !legacy) return ST_TOO_FEW_RELIABLE;
+  // the kernels' ladder (svoc/verdict.hpp), in consensus_fast_f32.hip's arithmetic
+  const RelF64 rel{constrained, rd, (double)max_spread, (int)N, (int)R};
+  const Verdict v = round_verdict(rel, sum_qr, sum_qr2, (int)R, legacy);
+  if (v.status != ST_OK) return v.status;
+  const float rel1 = v.rel1, rel2 = v.rel2;
   col.resize(R);
   const int64_t m2 = R / 2;
   for (int64_t d = 0; d < D; ++d) {

@@ -41,8 +41,9 @@
 #include "svoc/bufload.hpp"
 #include "svoc/route.hpp"
 #include "svoc/sortnet.hpp"
+#include "svoc/rankmask.hpp"
 #include "svoc/status.hpp"
-
+#include "svoc/verdict.hpp"
 
 namespace svoc {
 
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(1)))
   // r2_f32_keep_raw_ab.txt, r2_f32_raw_nseg_ab.txt)
   constexpr bool KEEP_RAW = true;
   __shared__ float qr_part[WAVES * NPAD];
-  __shared__ float qr_lds[NPAD];
+  __shared__ __attribute__((aligned(16))) float qr_lds[NPAD];   // (float4 reads: rank_mask_general)
   constexpr int NM = NSEG < 4 ? 4 : NSEG;   // 64-row mask words
   __shared__ uint64_t relmask[NM], lowmask[NM];
   __shared__ float rels[2];
@@ -208,78 +209,26 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(1)))
     for (int k = 0; k < KEEP; ++k) qr_part[wave * NPAD + seg * 64 + base + k] = acc[k];
   }
   __syncthreads();
-  for (int t = tid; t < NPAD; t += NT) {
-    float v = 0.f;
-    if (MODE == 2) {
-      v = t < N ? p.qr[(int64_t)b * N + t] : 0.f;
-    } else {
-#pragma unroll
-      for (int w = 0; w < WAVES; ++w) v += qr_part[w * NPAD + t];
-    }
-    qr_lds[t] = v;
-  }
-  __syncthreads();
-  if (MODE == 1) {   // D-sharding, first half: this shard's qr partials out (c1 already written)
-    for (int t = tid; t < N; t += NT) p.qr[(int64_t)b * N + t] = qr_lds[t];
-    if (tid == 0) p.status[b] = ST_OK;
-    return;
-  }
+  // (MODE 1, the D-sharded first half, ends here: c1 is already written)
+  if (reduce_qr<NT, NPAD, WAVES, MODE>(p, b, N, tid, qr_part, qr_lds)) return;
 
-  // ------------------------------------------------------------ rank mask (contract.cairo:345-363)
+  // ------------------------------------------------------------ rank mask, verdict (rankmask.hpp, verdict.hpp)
   const int R = N - p.n_failing;
-  for (int base = 0; base < NPAD; base += NT) {
-    const int t = base + tid;
-    bool rel = false;
-    if (t < N) {
-      const float myq = qr_lds[t];
-      int rank = 0;
-      for (int j = 0; j < N; ++j) {
-        const float qj = qr_lds[j];
-        rank += (qj < myq || (qj == myq && j > t)) ? 1 : 0;   // (qr asc, idx desc)
-      }
-      rel = rank < R;
-    }
-    const uint64_t bal = __ballot(rel);
-    if (lane == 0 && (t >> 6) < NM) relmask[t >> 6] = bal;
-  }
+  rank_mask_general<NT, NPAD, NM>(qr_lds, N, R, tid, relmask);
   __syncthreads();
   if (tid == 0) {
-    // reliabilities in fp64 over the fp32 qr, in the CPU twin's order (reference_cpu.cpp:224-243)
+    // fp64 sums of the fp32 qr, sequential: the CPU twin's order (reference_cpu.cpp fast_round_one)
     double s_all = 0.0, s_rel = 0.0;
     for (int t = 0; t < N; ++t) {
       s_all += (double)qr_lds[t];
       if ((relmask[t >> 6] >> (t & 63)) & 1) s_rel += (double)qr_lds[t];
     }
-    const double rd = p.legacy ? 1.0 : (double)(p.rel_dim > 0 ? p.rel_dim : D);
-    const double ms = (double)p.max_spread;
-    auto rel_of = [&](double mean_qr) -> float {
-      return CONS ? (float)(1.0 - 2.0 * sqrt(mean_qr / rd)) : (float)(1.0 - fmin(ms, sqrt(mean_qr)) / ms);
-    };
-    int st = ST_OK;
-    const float rel1 = rel_of(s_all / (double)N);
-    float rel2 = 0.f;
-    if (!(rel1 >= 0.f && rel1 <= 1.f)) st = ST_RELIABILITY_INTERVAL;
-    else if (R < 2) st = R == 0 ? ST_USIZE_UNDERFLOW : ST_INDEX_OOB;
-    else {
-      rel2 = rel_of(s_rel / (double)R);
-      if (!(rel2 >= 0.f && rel2 <= 1.f)) st = ST_RELIABILITY_INTERVAL;
-      else if (R < 4 && !p.legacy) st = ST_TOO_FEW_RELIABLE;
-    }
-    rels[0] = rel1;
-    rels[1] = rel2;
-    st_sh = st;
-    // pass-2 sentinel split: the first (NPAD - R + 1) / 2 non-reliable rows (row order) sort low
-    int need = (NPAD - R + 1) >> 1;
-    for (int w = 0; w < NM; ++w) {
-      uint64_t nr = w < NSEG ? ~relmask[w] : 0ull, lm = 0ull;
-      while (need > 0 && nr) {
-        const uint64_t bit = nr & (0ull - nr);
-        lm |= bit;
-        nr ^= bit;
-        --need;
-      }
-      lowmask[w] = lm;
-    }
+    const RelF64 rel{CONS, rel_divisor<double>(p.legacy, p.rel_dim, D), (double)p.max_spread, N, R};
+    const Verdict v = round_verdict(rel, s_all, s_rel, R, p.legacy);
+    rels[0] = v.rel1;
+    rels[1] = v.rel2;
+    st_sh = v.status;
+    low_sentinel_mask<NSEG, NM>(relmask, (NPAD - R + 1) >> 1, lowmask);
   }
   __syncthreads();
   if (st_sh != ST_OK) {

@@ -14,7 +14,9 @@
 #include "svoc/bufload.hpp"
 #include "svoc/launch.hpp"
 #include "svoc/sortnet.hpp"
+#include "svoc/rankmask.hpp"
 #include "svoc/status.hpp"
+#include "svoc/verdict.hpp"
 
 namespace svoc {
 
@@ -167,32 +169,9 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(NSEG
     return;
   }
 
-  // ------------------------------------------------------------ rank mask (contract.cairo:345-363)
+  // ------------------------------------------------------------ rank mask, verdict (rankmask.hpp, verdict.hpp)
   const int R = N - p.n_failing;
-  for (int base = 0; base < NPAD; base += NT) {  // NT >= 64: one ballot word per wave-chunk
-    const int t = base + tid;
-    bool rel = false;
-    float myq = 0.f;
-    if (t < N) {
-      myq = qr_lds[t];
-      int rank = 0;
-      const int n4 = N & ~3;
-      for (int j = 0; j < n4; j += 4) {
-        const float4 q4 = *(const float4*)(qr_lds + j);
-        rank += (q4.x < myq || (q4.x == myq && j > t)) ? 1 : 0;
-        rank += (q4.y < myq || (q4.y == myq && j + 1 > t)) ? 1 : 0;
-        rank += (q4.z < myq || (q4.z == myq && j + 2 > t)) ? 1 : 0;
-        rank += (q4.w < myq || (q4.w == myq && j + 3 > t)) ? 1 : 0;
-      }
-      for (int j = n4; j < N; ++j) {
-        const float qj = qr_lds[j];
-        rank += (qj < myq || (qj == myq && j > t)) ? 1 : 0;
-      }
-      rel = rank < R;
-    }
-    const uint64_t bal = __ballot(rel);
-    if (lane == 0 && (t >> 6) < MW) relmask[t >> 6] = bal;
-  }
+  rank_mask_general<NT, NPAD, MW>(qr_lds, N, R, tid, relmask);
   __syncthreads();
   if (tid < 64) {
     float s_all = 0.f, s_rel = 0.f;
@@ -207,34 +186,12 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(NSEG
       s_rel += __shfl_xor(s_rel, o);
     }
     if (tid == 0) {
-      // pass-2 sentinel split: the first (NPAD - R) / 2 non-reliable rows become -inf
-      int need = (NPAD - (N - p.n_failing) + 1) >> 1;
-      for (int w = 0; w < MW; ++w) {
-        uint64_t nr = w < NSEG ? ~relmask[w] : 0ull, lm = 0ull;
-        while (need > 0 && nr) {
-          const uint64_t bit = nr & (0ull - nr);
-          lm |= bit;
-          nr ^= bit;
-          --need;
-        }
-        lowmask[w] = lm;
-      }
-      int st = ST_OK;
-      const float rd = p.legacy ? 1.f : (float)(p.rel_dim > 0 ? p.rel_dim : D);
-      float rel1, rel2 = 0.f;
-      if (CONS) rel1 = 1.f - 2.f * sqrtf(s_all / (float)N / rd);
-      else rel1 = 1.f - fminf(p.max_spread, sqrtf(s_all / (float)N)) / p.max_spread;
-      if (!(rel1 >= 0.f && rel1 <= 1.f)) st = ST_RELIABILITY_INTERVAL;
-      else if (R < 2) st = R <= 0 ? ST_USIZE_UNDERFLOW : ST_INDEX_OOB;
-      else {
-        if (CONS) rel2 = 1.f - 2.f * sqrtf(s_rel / (float)R / rd);
-        else rel2 = 1.f - fminf(p.max_spread, sqrtf(s_rel / (float)R)) / p.max_spread;
-        if (!(rel2 >= 0.f && rel2 <= 1.f)) st = ST_RELIABILITY_INTERVAL;
-        else if (R < 4 && !p.legacy) st = ST_TOO_FEW_RELIABLE;  // legacy: no moments
-      }
-      misc_f[0] = rel1;
-      misc_f[1] = rel2;
-      misc_i[0] = st;
+      low_sentinel_mask<NSEG, MW>(relmask, (NPAD - R + 1) >> 1, lowmask);
+      const RelF32 rel{CONS, rel_divisor<float>(p.legacy, p.rel_dim, D), p.max_spread, N, R};
+      const Verdict v = round_verdict(rel, s_all, s_rel, R, p.legacy);
+      misc_f[0] = v.rel1;
+      misc_f[1] = v.rel2;
+      misc_i[0] = v.status;
       misc_i[1] = 0;
     }
   }
@@ -250,9 +207,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(NSEG
   const float n = (float)R;
   const uint64_t mymask = relmask[seg];
   const uint64_t mylow = lowmask[seg];
-  int first_rel = 0;
-  for (int w = 0; w < MW; ++w)
-    if (relmask[w]) { first_rel = 64 * w + __builtin_ctzll(relmask[w]); break; }
+  const int first_rel = first_reliable_row<MW>(relmask);
 
   // ------------------------------------------------------------ pass 2 (contract.cairo:476-500)
 #pragma nounroll

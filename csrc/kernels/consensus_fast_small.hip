@@ -22,6 +22,7 @@
 #include "svoc/launch.hpp"
 #include "svoc/sortnet.hpp"
 #include "svoc/status.hpp"
+#include "svoc/verdict.hpp"
 
 namespace svoc {
 
@@ -151,23 +152,11 @@ __global__ __launch_bounds__(256) void consensus_fast_small_kernel(FastParams p)
     relbits |= rel ? (1u << i) : 0u;
     s_rel += rel ? qr[i] : 0.f;
   }
-  // divisors are launch-uniform: one reciprocal each instead of a full-precision division per use
-  // (the divisions were ~20% of this kernel's VALU instructions; profiles/r2_pmc_c5.md)
-  const float rd = p.legacy ? 1.f : (float)(p.rel_dim > 0 ? p.rel_dim : D);
-  const float inv_nrd = 1.f / ((float)N * rd), inv_rrd = 1.f / ((float)R * rd);
-  const float inv_ms = 1.f / p.max_spread;
-  int st = ST_OK;
-  float rel1, rel2 = 0.f;
-  if (CONS) rel1 = 1.f - 2.f * sqrtf(s_all * inv_nrd);
-  else rel1 = 1.f - fminf(p.max_spread, sqrtf(s_all * (1.f / (float)N))) * inv_ms;
-  if (!(rel1 >= 0.f && rel1 <= 1.f)) st = ST_RELIABILITY_INTERVAL;
-  else if (R < 2) st = R <= 0 ? ST_USIZE_UNDERFLOW : ST_INDEX_OOB;
-  else {
-    if (CONS) rel2 = 1.f - 2.f * sqrtf(s_rel * inv_rrd);
-    else rel2 = 1.f - fminf(p.max_spread, sqrtf(s_rel * (1.f / (float)R))) * inv_ms;
-    if (!(rel2 >= 0.f && rel2 <= 1.f)) st = ST_RELIABILITY_INTERVAL;
-    else if (R < 4 && !p.legacy) st = ST_TOO_FEW_RELIABLE;
-  }
+  // verdict (verdict.hpp), with reciprocals of the launch-uniform divisors
+  const RelF32Rcp rel(CONS, rel_divisor<float>(p.legacy, p.rel_dim, D), p.max_spread, N, R);
+  const Verdict v = round_verdict(rel, s_all, s_rel, R, p.legacy);
+  const int st = v.status;
+  const float rel1 = v.rel1, rel2 = v.rel2;
   if (st != ST_OK) {  // revert: only the status is written (and the pass-1 c1 when the caller took it unstaged)
     if (live && g == 0) p.status[b] = st;
     return;           // uniform over the group

@@ -38,6 +38,7 @@
 #include "svoc/rankmask.hpp"
 #include "svoc/sortnet.hpp"
 #include "svoc/status.hpp"
+#include "svoc/verdict.hpp"
 
 namespace svoc {
 
@@ -595,52 +596,16 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
     for (int i = 0; i < KEEP; ++i) qr_part[wave * NPAD + seg * 64 + base + i] = keep[i];
   }
   __syncthreads();
-  for (int t = tid; t < NPAD; t += NT) {
-    float q = 0.f;
-    if (MODE == 2) {
-      q = t < N ? p.qr[(int64_t)b * N + t] : 0.f;
-    } else {
-#pragma unroll
-      for (int w = 0; w < WAVES; ++w) q += qr_part[w * NPAD + t];
-    }
-    qr_lds[t] = q;
-  }
-  __syncthreads();
-  if (MODE == 1) {
-    for (int t = tid; t < N; t += NT) p.qr[(int64_t)b * N + t] = qr_lds[t];
-    if (tid == 0) p.status[b] = ST_OK;
-    return;
-  }
+  if (reduce_qr<NT, NPAD, WAVES, MODE>(p, b, N, tid, qr_part, qr_lds)) return;
 
-  // ------------------------------------------------------------ rank mask (contract.cairo:345-363)
+  // ------------------------------------------------------------ rank mask, verdict (rankmask.hpp, verdict.hpp)
   const int f = p.n_failing;
   const int R = N - f;
   if constexpr (CONS) {
     static_assert(WAVES >= 2, "rank keys in qr_part");
     rank_mask_nonneg<NT, NPAD>(qr_lds, reinterpret_cast<uint64_t*>(qr_part), N, R, tid, relmask);
-  } else
-  for (int base = 0; base < NPAD; base += NT) {
-    const int t = base + tid;
-    bool rel = false;
-    if (t < N) {
-      const float myq = qr_lds[t];
-      int rank = 0;
-      const int n4 = N & ~3;
-      for (int j = 0; j < n4; j += 4) {
-        const float4 q4 = *(const float4*)(qr_lds + j);
-        rank += (q4.x < myq || (q4.x == myq && j > t)) ? 1 : 0;
-        rank += (q4.y < myq || (q4.y == myq && j + 1 > t)) ? 1 : 0;
-        rank += (q4.z < myq || (q4.z == myq && j + 2 > t)) ? 1 : 0;
-        rank += (q4.w < myq || (q4.w == myq && j + 3 > t)) ? 1 : 0;
-      }
-      for (int j = n4; j < N; ++j) {
-        const float qj = qr_lds[j];
-        rank += (qj < myq || (qj == myq && j > t)) ? 1 : 0;
-      }
-      rel = rank < R;
-    }
-    const uint64_t bal = __ballot(rel);
-    if (lane == 0 && (t >> 6) < 4) relmask[t >> 6] = bal;
+  } else {
+    rank_mask_general<NT, NPAD, 4>(qr_lds, N, R, tid, relmask);
   }
   __syncthreads();
   // removed rows in index order (pass 2 reads only these)
@@ -667,24 +632,11 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
       s_rel += __shfl_xor(s_rel, o);
     }
     if (tid == 0) {
-      int st = ST_OK;
-      const double rd = p.legacy ? 1.0 : (double)(p.rel_dim > 0 ? p.rel_dim : D);
-      const double ms = (double)p.max_spread;
-      auto rel_of = [&](double mean_qr) -> float {
-        return CONS ? (float)(1.0 - 2.0 * sqrt(mean_qr / rd)) : (float)(1.0 - fmin(ms, sqrt(mean_qr)) / ms);
-      };
-      const float rel1 = rel_of(s_all / (double)N);
-      float rel2 = 0.f;
-      if (!(rel1 >= 0.f && rel1 <= 1.f)) st = ST_RELIABILITY_INTERVAL;
-      else if (R < 2) st = R <= 0 ? ST_USIZE_UNDERFLOW : ST_INDEX_OOB;
-      else {
-        rel2 = rel_of(s_rel / (double)R);
-        if (!(rel2 >= 0.f && rel2 <= 1.f)) st = ST_RELIABILITY_INTERVAL;
-        else if (R < 4 && !p.legacy) st = ST_TOO_FEW_RELIABLE;
-      }
-      misc_f[0] = rel1;
-      misc_f[1] = rel2;
-      misc_i[0] = st;
+      const RelF64 rel{CONS, rel_divisor<double>(p.legacy, p.rel_dim, D), (double)p.max_spread, N, R};
+      const Verdict v = round_verdict(rel, s_all, s_rel, R, p.legacy);
+      misc_f[0] = v.rel1;
+      misc_f[1] = v.rel2;
+      misc_i[0] = v.status;
       misc_i[1] = 0;
     }
   }
@@ -702,9 +654,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
   // compared against the reliable rows (as consensus_fast_win.hip).  Decided before any output is written.
   if (CONS && !p.legacy) {
     const bool inwin = f + H <= N / 2;
-    int fr = 0;   // first reliable row
-    for (int w = 0; w < 4; ++w)
-      if (relmask[w]) { fr = 64 * w + __builtin_ctzll(relmask[w]); break; }
+    const int fr = first_reliable_row<4>(relmask);
     bool zv = false;
 #pragma nounroll
     for (int base = wave * 64; base < D; base += WAVES * 64) {
