@@ -47,11 +47,19 @@ struct RelF32Rcp {
   SVOC_HD RelF32Rcp(bool cons_, float rd, float ms_, int N_, int R_)
       : cons(cons_), ms(ms_), inv_nrd(1.f / ((float)N_ * rd)), inv_rrd(1.f / ((float)R_ * rd)), inv_ms(1.f / ms_),
         N(N_), R(R_) {}
+  // Unconstrained, sd = sqrt(s / n).  Where the spread is clamped (sd >= ms) the contract's value is 1 - ms / ms = 0,
+  // but 1 - ms * inv_ms is contracted to fma(-ms, inv_ms, 1): the exact residual of the rounded reciprocal, below
+  // zero for every ms whose reciprocal rounds up (3, 5, 24, 0.3 ...) -- a RELIABILITY_INTERVAL revert of a round
+  // the contract commits.  The clamped residual is floored at 0; every other value (NaN included) is as it was.
+  SVOC_HD float unc(float sd) const {
+    const float r = 1.f - fminf(ms, sd) * inv_ms;
+    return sd >= ms && r < 0.f ? 0.f : r;
+  }
   SVOC_HD float rel1(float s_all) const {
-    return cons ? 1.f - 2.f * sqrtf(s_all * inv_nrd) : 1.f - fminf(ms, sqrtf(s_all * (1.f / (float)N))) * inv_ms;
+    return cons ? 1.f - 2.f * sqrtf(s_all * inv_nrd) : unc(sqrtf(s_all * (1.f / (float)N)));
   }
   SVOC_HD float rel2(float s_rel) const {
-    return cons ? 1.f - 2.f * sqrtf(s_rel * inv_rrd) : 1.f - fminf(ms, sqrtf(s_rel * (1.f / (float)R))) * inv_ms;
+    return cons ? 1.f - 2.f * sqrtf(s_rel * inv_rrd) : unc(sqrtf(s_rel * (1.f / (float)R)));
   }
 };
 

@@ -8,9 +8,9 @@ kernel).  Negative bf16 / fp32 sort keys, the sentinel split of the padding rows
 reliable, c1 and the constrained consensus bit for bit; the unconstrained mean within the forward
 bound of an fp32 sum; qr, rel and the moments within the project's fast-mode tolerances.
 
-Known untested edge: unconstrained values so large that a squared deviation overflows fp32.  The
-padding rows of the small kernel's rank count sit at +inf and would tie with such rows.  Non-finite
-inputs are rejected by the update kernels and are not tested here either.
+Unconstrained values so large that a deviation power overflows fp32 (qr = +inf, which ties with the
+padding rows of the small kernel's rank count) are test_fast_extreme.py's and test_fast_extreme_gpu.py's.
+Non-finite inputs are rejected by the update kernels and are not tested here either.
 """
 import pytest
 import torch
