@@ -86,4 +86,15 @@ int fast_round_one(const float* X, int64_t N, int64_t D, int64_t n_failing, bool
                    float max_spread, FastOut& o, int mode = 0, int64_t rel_dim = 0, bool legacy = false);
 void fast_round_batch_cpu(const FastBatch& b, int threads);
 
+// ---- rank-weighted (L-estimator) rounds: CPU twin of consensus_fast_lest.hip --------------------
+// A whole fast round (fp32 values, the current contract) whose essence estimator is sum_k w[k] x(k) over the
+// sorted column: w1 [N] in pass 1, w2 [N - n_failing] in the constrained pass 2.  Full std::sort per column, the
+// weighted sum an fp32 fma chain in ascending rank; the rest is fast_round_one's arithmetic.
+constexpr int64_t kLestWeightPitch = 256;   // floats per row of the op's [2, 256] weight tensor
+int lest_round_one(const float* X, int64_t N, int64_t D, int64_t n_failing, bool constrained, float max_spread,
+                   const float* w1, const float* w2, FastOut& o);
+// weights: [2, kLestWeightPitch] (row 0 = w1, row 1 = w2).  FastBatch.mode / rel_dim / legacy are not read; c1 is
+// written, like every output, only where the round succeeded.
+void lest_round_batch_cpu(const FastBatch& b, const float* weights, int threads);
+
 }  // namespace svoc

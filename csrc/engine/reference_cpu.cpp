@@ -307,4 +307,110 @@ void fast_round_batch_cpu(const FastBatch& b, int threads) {
   });
 }
 
+// ------------------------------------------------------------------------------------------------
+// Rank-weighted (L-estimator) round: fast_round_one with sum_k w[k] x(k) over the sorted column in place of the
+// smooth median; mirrors consensus_fast_lest.hip.
+// ------------------------------------------------------------------------------------------------
+
+namespace {
+
+// fp32 fma chain in ascending rank over the sorted column; a zero weight contributes exactly zero (its value,
+// finite or not, is not read)
+float rank_weighted(std::vector<float>& col, const float* w) {
+  std::sort(col.begin(), col.end());
+  float acc = 0.f;
+  for (size_t k = 0; k < col.size(); ++k)
+    if (w[k] != 0.f) acc = std::fma(w[k], col[k], acc);
+  return acc;
+}
+
+}  // namespace
+
+int lest_round_one(const float* X, int64_t N, int64_t D, int64_t n_failing, bool constrained, float max_spread,
+                   const float* w1, const float* w2, FastOut& o) {
+  if (n_failing > N) return ST_USIZE_UNDERFLOW;
+  if (N < 2) return ST_INDEX_OOB;
+  std::vector<float> col(N);
+  const double rd = rel_divisor<double>(false, (int64_t)0, D);
+  for (int64_t d = 0; d < D; ++d) {
+    for (int64_t i = 0; i < N; ++i) col[i] = X[i * D + d];
+    o.c1[d] = rank_weighted(col, w1);
+  }
+  double sum_qr = 0.0;
+  for (int64_t i = 0; i < N; ++i) {
+    float acc = 0.f;
+    for (int64_t d = 0; d < D; ++d) {
+      float y = X[i * D + d] - o.c1[d];
+      acc = std::fma(y, y, acc);
+    }
+    o.qr[i] = acc;
+    sum_qr += o.qr[i];
+  }
+  std::vector<int64_t> order(N);
+  std::iota(order.begin(), order.end(), 0);
+  std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+    return o.qr[a] != o.qr[b] ? o.qr[a] < o.qr[b] : a > b;
+  });
+  const int64_t R = N - n_failing;
+  for (int64_t r = 0; r < N; ++r) o.reliable[order[r]] = r < R ? 1 : 0;
+  double sum_qr2 = 0.0;
+  for (int64_t i = 0; i < N; ++i)
+    if (o.reliable[i]) sum_qr2 += o.qr[i];
+  const RelF64 rel{constrained, rd, (double)max_spread, (int)N, (int)R};
+  const Verdict v = round_verdict(rel, sum_qr, sum_qr2, (int)R, false);
+  if (v.status != ST_OK) return v.status;
+  col.resize(R);
+  for (int64_t d = 0; d < D; ++d) {
+    int64_t k = 0;
+    for (int64_t i = 0; i < N; ++i)
+      if (o.reliable[i]) col[k++] = X[i * D + d];
+    double mean = 0.0;
+    for (float x : col) mean += x;
+    mean /= (double)R;
+    double s2 = 0, s3 = 0, s4 = 0;
+    for (float x : col) {
+      double y = x - mean;
+      s2 += y * y;
+      s3 += y * y * y;
+      s4 += y * y * y * y;
+    }
+    const double var = s2 / (double)R;
+    // a constant reliable column is decided exactly (the fp64 mean of R equal values may round off it)
+    const bool constant = *std::min_element(col.begin(), col.end()) == *std::max_element(col.begin(), col.end());
+    if (constant || var <= 0.0) return ST_ZERO_VARIANCE;
+    const double sd = std::sqrt(var);
+    const double z3 = s3 / (sd * sd * sd), z4 = s4 / (var * var);
+    const double n = (double)R;
+    o.skew[d] = (float)(z3 * n / ((n - 1) * (n - 2)));
+    o.kurt[d] = (float)(((z4 * n * (n + 1)) / (n - 1) - 3.0 * (n - 1) * (n - 1)) / ((n - 2) * (n - 3)));
+    o.consensus[d] = constrained ? rank_weighted(col, w2) : (float)mean;
+  }
+  o.rel1 = v.rel1;
+  o.rel2 = v.rel2;
+  return ST_OK;
+}
+
+void lest_round_batch_cpu(const FastBatch& b, const float* weights, int threads) {
+  parallel_for(b.B, threads, [&](int64_t i) {
+    if (b.active && !b.active[i]) return;
+    const int64_t N = b.N, D = b.D;
+    std::vector<float> x(N * D), c1(D), cons(D), sk(D), ku(D), qr(N);
+    std::vector<uint8_t> rel(N);
+    b.load(b.values, i, x.data());
+    FastOut o{c1.data(), qr.data(), rel.data(), cons.data(), sk.data(), ku.data(), 0.f, 0.f};
+    const int st = lest_round_one(x.data(), N, D, b.n_failing, b.constrained, b.max_spread, weights,
+                                  weights + kLestWeightPitch, o);
+    b.status[i] = st;
+    if (st != ST_OK) return;   // revert: no output written
+    std::memcpy(b.c1 + i * D, c1.data(), D * sizeof(float));
+    std::memcpy(b.consensus + i * D, cons.data(), D * sizeof(float));
+    std::memcpy(b.skew + i * D, sk.data(), D * sizeof(float));
+    std::memcpy(b.kurt + i * D, ku.data(), D * sizeof(float));
+    std::memcpy(b.qr + i * N, qr.data(), N * sizeof(float));
+    std::memcpy(b.reliable + i * N, rel.data(), N);
+    b.rel[i * 2 + 0] = o.rel1;
+    b.rel[i * 2 + 1] = o.rel2;
+  });
+}
+
 }  // namespace svoc

@@ -101,6 +101,13 @@ inline int fast_win_h(int N, int f) {
   return 0;
 }
 
+// Rank-weighted round (consensus_fast_lest.hip): a fast fp32 round (mode 0, c1 staged and c1_out set, a workspace)
+// plus the weights per rank, [2, 256] fp32 on the device: row 0 weighs pass 1's N ranks, row 1 pass 2's N - f.
+struct LestParams {
+  FastParams f;
+  const float* weights;
+};
+
 struct ExactParams {
   const void* values;       // [B, N, D] wsad, int64 (or int32 when val32)
   const uint8_t* active;    // [B] or null
@@ -160,6 +167,7 @@ typedef struct ihipStream_t* hipStream_t;
 int svoc_fast_round_bf16(const svoc::FastParams* p, hipStream_t stream);
 int svoc_fast_round_f32(const svoc::FastParams* p, hipStream_t stream);   // values fp32 [B, N, ld]
 int svoc_fast_round_f32_win(const svoc::FastParams* p, hipStream_t stream);
+int svoc_lest_round_f32(const svoc::LestParams* p, hipStream_t stream);     // values fp32 [B, N, ld]
 int svoc_exact_round(const svoc::ExactParams* p, hipStream_t stream);
 // Verdict of a whole round: status, and rel where it is OK; no other output is produced where the verdict form
 // of the column kernel applies (svoc_exact_verdict_applies: the caller then passes `fallback` and no `stage`).

@@ -77,6 +77,29 @@ inline FastShape fast_shape(const FastParams& p, int storage) {
           !p.work ? kWorkNone : p.work_fresh ? kWorkFresh : kWorkCaller};
 }
 
+// ------------------------------------------------------------------------------- rank-weighted (L-estimator) rounds
+// consensus_fast_lest.hip: a weight per rank instead of the smooth median's middle pair.  fp32 storage, whole rounds,
+// the current contract only; every rank of a column is sorted, at 64 rows per lane and at most 4 lanes per column.
+constexpr int kLestMaxN = 256;
+
+struct LestRoute {
+  int supported;     // the kernel takes this shape
+  int lane_groups;   // its NSEG: 1 / 2 / 4
+  int max_n;         // kLestMaxN
+  int needs_work;    // it stages its outputs in the workspace (always)
+};
+
+inline LestRoute lest_route(const FastShape& s) {
+  LestRoute r{};
+  r.max_n = kLestMaxN;
+  r.needs_work = 1;
+  r.lane_groups = lane_groups(s.N);
+  r.supported = s.storage == kStoreF32 && s.N >= 2 && s.N <= kLestMaxN && s.D >= 1 && s.D <= s.ld &&
+                s.n_failing >= 0 && s.n_failing <= s.N - 2 && s.mode == 0 && !s.legacy &&
+                (int64_t)s.N * s.ld * 4 < (1ll << 31);   // 32-bit buffer offsets, as fast_route
+  return r;
+}
+
 // ------------------------------------------------------------------------------------------------ exact rounds
 constexpr int kWsadMinD = 64;   // fewest columns the column kernel takes for N <= 32 (one lane per column)
 

@@ -23,9 +23,10 @@ class ConsensusService:
     """B contracts sharing one configuration. ``mode='exact'`` is bit-compatible with the contract."""
 
     def __init__(self, cfg: ConsensusConfig, batch: int, admins, oracles, device="cpu", mode: str = "exact",
-                 storage=None):
+                 storage=None, rank_weights=None):
         self.cfg = cfg
-        self.engine = ConsensusEngine(cfg, batch, device=device, mode=mode, storage=storage)
+        # (rank_weights: the engine's explicit L-estimator weights, with cfg.essence == "rank_weighted")
+        self.engine = ConsensusEngine(cfg, batch, device=device, mode=mode, storage=storage, rank_weights=rank_weights)
         e = self.engine
         track = ({"rounds": e.track_rounds, "flagged": e.track_flagged, "streak": e.track_streak,
                   "score": e.track_score, "since": e.track_since} if cfg.track_oracles else None)

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import dataclasses
 import json
+import math
 from typing import Any, Dict, Optional
 
 WSAD = 1_000_000
@@ -35,8 +36,19 @@ class ConsensusConfig:
     # failing-only replacement (documentation/README.md:114,167-172): a voted replacement applies only to a
     # seat flagged unreliable in its last k committed rounds; 0 = off.  Needs track_oracles.
     replace_only_failing: int = 0
+    # essence estimator of the fast rounds: "smooth_median" (the contract's: the mean of the two middle order
+    # statistics) or "rank_weighted" (the super smooth median of documentation/README.md:150: a bell-weighted sum
+    # over the ranks, svoc.estimators.rank_weights; fp32 storage, up to 256 oracles).  rank_sigma: the bell's width
+    # as a fraction of the count.
+    essence: str = "smooth_median"
+    rank_sigma: float = 0.125
 
     def validate(self) -> None:
+        if self.essence not in ("smooth_median", "rank_weighted"):
+            raise ValueError(f"unknown essence estimator {self.essence!r} ('smooth_median' or 'rank_weighted')")
+        if (isinstance(self.rank_sigma, bool) or not isinstance(self.rank_sigma, (int, float))
+                or not math.isfinite(self.rank_sigma) or self.rank_sigma <= 0):
+            raise ValueError("rank_sigma must be a finite number > 0")
         if self.n_oracles < 1 or self.dimension < 1:
             raise ValueError("n_oracles and dimension must be >= 1")
         if not (0 <= self.n_admins <= 64):

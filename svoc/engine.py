@@ -41,6 +41,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
+from . import estimators
 from . import ops as svops
 from .config import WSAD, ConsensusConfig
 from .status import Status
@@ -134,10 +135,15 @@ class _PendingBatches:
 
 class ConsensusEngine:
     def __init__(self, cfg: ConsensusConfig, batch: int, device="cuda", mode: str = "fast",
-                 storage: Optional[str] = None):
+                 storage: Optional[str] = None, rank_weights=None):
+        """``rank_weights=(w1, w2)`` (only with ``cfg.essence == "rank_weighted"``): explicit weights per rank for
+        pass 1 (``n_oracles`` of them) and pass 2 (``n_oracles - n_failing_oracles``) instead of the bell of
+        ``cfg.rank_sigma`` -- the general L-estimator (svoc.estimators: a trimmed mean, an order statistic ...).
+        Each row: finite, non-negative, summing to 1 within 1e-5."""
         cfg.validate()
         if mode not in ("fast", "exact"):
             raise ValueError("mode must be 'fast' or 'exact'")
+        lest_rows = self._lest_rows(cfg, mode, storage, rank_weights)
         self.cfg = cfg
         self.B = int(batch)
         self.N = cfg.n_oracles
@@ -180,6 +186,14 @@ class ConsensusEngine:
         self.wave_hint = 0
         self.rounds = 0
         self.failing_mask: Optional[torch.Tensor] = None   # [B, N] set by randomize()
+        # rank-weighted essence (cfg.essence == "rank_weighted"): the op's [2, 256] weights (row 0 pass 1, row 1
+        # pass 2), built on the host and uploaded once; None: the smooth median (fast_round)
+        self._lest = None
+        self._lest_route = None               # svops.LestRoute of such an engine
+        self._lest_explicit = rank_weights is not None
+        if lest_rows is not None:
+            self._lest = estimators.pack(*lest_rows[0]).to(dev)
+            self._lest_route = lest_rows[1]
         self._work = None   # fast kernels' workspace (GPU fast mode), allocated on first use
         self._routes: Dict[int, tuple] = {}   # wave_hint -> svops.FastRoute (_route)
         self._xroute = None                   # svops.ExactRoute (_verdict_ok)
@@ -223,6 +237,45 @@ class ConsensusEngine:
             self.track_streak = torch.zeros(B, N, dtype=torch.int32, device=dev)
             self.track_score = torch.zeros(B, N, dtype=torch.int64, device=dev)
             self.track_since = torch.zeros(B, N, dtype=torch.int32, device=dev)
+
+    # ------------------------------------------------------------------ rank-weighted essence
+    @staticmethod
+    def _lest_rows(cfg: ConsensusConfig, mode: str, storage: Optional[str], rank_weights):
+        """``((w1, w2), route)`` of a ``rank_weighted`` engine -- the two validated weight rows (fp32, CPU) and its
+        svops.LestRoute -- or None for the smooth median.  Raises ValueError where the rank-weighted round does not
+        exist: exact mode, and whatever the route refuses (bf16 storage, the legacy contracts, the oracle counts)."""
+        if cfg.essence != "rank_weighted":
+            if rank_weights is not None:
+                raise ValueError("rank_weights needs cfg.essence == 'rank_weighted'")
+            return None
+        if mode != "fast":
+            raise ValueError("essence='rank_weighted' is a fast-mode estimator (mode='fast'): the exact engine "
+                             "computes the contract's smooth median")
+        storage = storage or "bf16"
+        if storage not in svops.STORAGE:
+            raise ValueError(f"unknown fast-mode storage {storage!r}")
+        # what the round takes is stated once, in route.hpp (lest_route): storage, the oracle counts, the variant
+        n, f = cfg.n_oracles, cfg.n_failing_oracles
+        route = svops.lest_route(storage, n, cfg.dimension, _round_up(cfg.dimension, 8), f, cfg.constrained, cfg.legacy)
+        if not route.supported:
+            raise ValueError(f"essence='rank_weighted' is not available for this engine: its round takes fp32 storage "
+                             f"(storage='fp32'), the current contract variant, 2 <= n_oracles <= {route.max_n} and 0 <= "
+                             f"n_failing_oracles <= n_oracles - 2 (got storage={storage!r}, variant={cfg.variant!r}, "
+                             f"n_oracles={n}, n_failing_oracles={f})")
+        if rank_weights is None:
+            return estimators.round_weights(n, f, cfg.rank_sigma), route
+        try:
+            w1, w2 = rank_weights
+        except (TypeError, ValueError):
+            raise ValueError("rank_weights: a pair (w1, w2)") from None
+        return (estimators.check_weights(w1, n, "rank_weights[0]"),
+                estimators.check_weights(w2, n - f, "rank_weights[1]")), route
+
+    def rank_weight_rows(self):
+        """``(w1, w2)`` of a ``rank_weighted`` engine (fp32, on the device), None otherwise."""
+        if self._lest is None:
+            return None
+        return self._lest[0, : self.N], self._lest[1, : self.N - self.cfg.n_failing_oracles]
 
     # ------------------------------------------------------------------ sizing
     @staticmethod
@@ -361,10 +414,21 @@ class ConsensusEngine:
             if w is not None and sl is not None:
                 words = w.numel() // self.B
                 w = w[sl.start * words:sl.stop * words]
-            self._ops.fast_round(v(self.values), active, self.D, self.cfg.n_failing_oracles, self.cfg.constrained,
-                                 float(self.cfg.unconstrained_max_spread), v(self.c1), v(self.consensus),
-                                 v(self.skew), v(self.kurt), v(self.rel), v(self.qr), v(self.reliable),
-                                 v(self.status), self.wave_hint, 0, 0, self.cfg.legacy, w, self._net_fb, **batch)
+            if self._lest is not None:
+                # rank-weighted essence: its own round kernel; a transactional step's rollback is `then` (the
+                # restore kernel), never the round's own (_fused_ok / _kernel_rollback_ok)
+                if batch:
+                    raise RuntimeError("the rank-weighted round takes no update / rollback batch")
+                self._ops.lest_round(v(self.values), active, self.D, self.cfg.n_failing_oracles, self.cfg.constrained,
+                                     float(self.cfg.unconstrained_max_spread), self._lest, v(self.c1),
+                                     v(self.consensus), v(self.skew), v(self.kurt), v(self.rel), v(self.qr),
+                                     v(self.reliable), v(self.status), w)
+            else:
+                self._ops.fast_round(v(self.values), active, self.D, self.cfg.n_failing_oracles,
+                                     self.cfg.constrained, float(self.cfg.unconstrained_max_spread), v(self.c1),
+                                     v(self.consensus), v(self.skew), v(self.kurt), v(self.rel), v(self.qr),
+                                     v(self.reliable), v(self.status), self.wave_hint, 0, 0, self.cfg.legacy, w,
+                                     self._net_fb, **batch)
         else:
             self._ops.exact_round(v(self.values), active, self.cfg.n_failing_oracles, self.cfg.constrained,
                                   self.cfg.max_spread_wsad, v(self.c1), v(self.consensus), v(self.skew), v(self.kurt),
@@ -419,6 +483,8 @@ class ConsensusEngine:
         route says so (the bf16 window kernel), U updates per instance, constrained rounds."""
         if os.environ.get("SVOC_KERNEL_ROLLBACK", "1") == "0":   # (A/B: the restore kernel instead)
             return False
+        if self._lest is not None:   # the rank-weighted round rolls nothing back: the restore kernel after it
+            return False
         return (self._gpu_fast() and bool(self._route().rollback) and 0 < U
                 # engine policy: the route also rolls back unconstrained rounds, ...
                 and self.cfg.constrained
@@ -436,6 +502,8 @@ class ConsensusEngine:
         (bf16 storage takes the generic path: the same fusion in the bf16 window kernel measured slower than
         saving the rows, profiles/r4_c3_bf16_txn_ab.txt.)"""
         if os.environ.get("SVOC_FUSED_TXN", "1") == "0":   # (A/B: the generic path instead)
+            return False
+        if self._lest is not None:   # the rank-weighted round reads no update batch: saved rows, then the restore
             return False
         if not (self._gpu_fast() and 0 < U <= self._route().fused_max_u
                 and vals.dtype == self.vdtype and vals.dim() == 2 and vals.shape[1] == self.D
@@ -632,7 +700,10 @@ class ConsensusEngine:
     def work(self) -> Optional[torch.Tensor]:
         """Workspace of the fast kernels (window keys, power sums, cleanup list and staged pass-2 outputs per
         column: launch.hpp fast_work_words); None where the route needs none (CPU, the small-instance kernel)."""
-        if not self._gpu_fast() or not self._route().needs_work:
+        if not self._gpu_fast():
+            return None
+        # (a rank-weighted engine asks its own round's route, not the smooth-median kernels')
+        if not (self._lest_route if self._lest is not None else self._route()).needs_work:
             return None
         if self._work is None:
             self._work = torch.empty(svops.fast_work_numel(self.B, self.D), dtype=torch.int32,
@@ -644,7 +715,7 @@ class ConsensusEngine:
         ``slab_networks`` run so far (processed rounds x full 64-column slab steps x 4 waves) and the
         ``fallbacks`` among them whose exact check failed (the full network reran for that wave)."""
         self.pipeline_join()
-        if self._net_fb is None or not self._route().pruned:
+        if self._net_fb is None or self._lest is not None or not self._route().pruned:
             return {"slab_networks": 0, "fallbacks": 0}
         processed = int(self.metrics_fx[2].item())
         return {"slab_networks": processed * (self.D // 64) * 4, "fallbacks": int(self._net_fb.item())}

@@ -100,6 +100,19 @@ def exact_route(N: int, D: int, elem_bytes: int, n_failing: int, constrained: bo
     return ExactRoute(*ops().exact_route(N, D, elem_bytes, n_failing, bool(constrained), bool(legacy), mode))
 
 
+class LestRoute(NamedTuple):
+    supported: int     # the rank-weighted kernel takes this shape
+    lane_groups: int   # 1 / 2 / 4
+    max_n: int         # most oracles it sorts per column
+    needs_work: int    # it stages its outputs in the workspace
+
+
+def lest_route(storage: str, N: int, D: int, ld: int, n_failing: int, constrained: bool, legacy: bool = False,
+               mode: int = 0) -> LestRoute:
+    """The route of a GPU rank-weighted round of this shape (route.hpp lest_route).  ``storage``: "bf16" / "fp32"."""
+    return LestRoute(*ops().lest_route(STORAGE[storage], N, D, ld, n_failing, bool(constrained), bool(legacy), mode))
+
+
 def fast_work_words(D: int) -> int:
     """u32 words per instance of the fast kernels' workspace (launch.hpp fast_work_words)."""
     return ops().fast_work_words(D)

@@ -99,8 +99,14 @@ def run_round_sharded(engine, d_global: int, group=None, world: int = 1, defer: 
     in the NEXT round's packed buffer, which commits this round before its own pass 2 (one collective
     per round).  A deferred round is pending until that next round or :func:`flush_sharded`; its
     instances' ``touched`` flags are cleared at once (the epilogue clears them anyway), so the next
-    round's selection is unchanged."""
+    round's selection is unchanged.
+
+    Raises NotImplementedError for a ``rank_weighted`` engine (``cfg.essence``): the rank-weighted round kernel runs
+    whole rounds only, it has no D-sharded halves."""
     e = engine
+    if getattr(e, "_lest", None) is not None:
+        raise NotImplementedError("run_round_sharded: the rank-weighted essence (cfg.essence='rank_weighted') has no "
+                                  "D-sharded halves")
     sh = e._dshard_shadow
     if sh is None:
         sh = e._dshard_shadow = _Shadow(e)

@@ -55,6 +55,11 @@ def save(svc, path: str) -> None:
     if e.tracking:
         # the per-oracle track record (cfg.track_oracles; not contract storage)
         secs += [("track_" + k, v, "") for k, v in e.track_record().items()]
+    if e._lest is not None:
+        # rank-weighted essence: the weights the rounds use, [2, 256] fp32 -- the bell of cfg.rank_sigma or the
+        # caller's explicit rows (meta: rank_weights_explicit); a reload runs on exactly these
+        meta["rank_weights_explicit"] = bool(e._lest_explicit)
+        secs.append(("rank_weights", e._lest, ""))
     if e.mode == "fast" and e._pending:
         # update batches awaiting their round (transactional steps): the pre-image their revert restores
         e._pending.fold()
@@ -88,9 +93,16 @@ def load(path: str, device="cpu"):
     B = int(meta["batch"])
     # placeholder addresses, then the checkpoint's limb tensors copied in directly (no per-instance
     # host conversion: a 1M-instance checkpoint restores in seconds)
+    rw = None
+    if cfg.essence == "rank_weighted" and "rank_weights" in t:
+        # the saved rows as explicit weights: the engine validates them again and runs on exactly these
+        w = t["rank_weights"].to(torch.float32)
+        rw = (w[0, : cfg.n_oracles], w[1, : cfg.n_oracles - cfg.n_failing_oracles])
     svc = ConsensusService(cfg, B, [0] * cfg.n_admins, [0] * cfg.n_oracles, device=device, mode=meta["mode"],
-                           storage=storage_of(meta))
+                           storage=storage_of(meta), rank_weights=rw)
     e, g = svc.engine, svc.gov
+    if rw is not None:
+        e._lest_explicit = bool(meta.get("rank_weights_explicit", False))
     dev = e.device
     if cfg.n_admins:
         g.admins.copy_(t["admins"].to(dev))
