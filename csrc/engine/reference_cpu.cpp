@@ -314,14 +314,14 @@ void fast_round_batch_cpu(const FastBatch& b, int threads) {
 
 namespace {
 
-// fp32 fma chain in ascending rank over the sorted column; a zero weight contributes exactly zero (its value,
-// finite or not, is not read)
+// fp64 fma chain in ascending rank over the sorted column (every product exact), rounded to fp32 once; a zero
+// weight contributes exactly zero (its value, finite or not, is not read)
 float rank_weighted(std::vector<float>& col, const float* w) {
   std::sort(col.begin(), col.end());
-  float acc = 0.f;
+  double acc = 0.0;
   for (size_t k = 0; k < col.size(); ++k)
-    if (w[k] != 0.f) acc = std::fma(w[k], col[k], acc);
-  return acc;
+    if (w[k] != 0.f) acc = std::fma((double)w[k], (double)col[k], acc);
+  return (float)acc;
 }
 
 }  // namespace

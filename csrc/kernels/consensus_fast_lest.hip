@@ -22,7 +22,8 @@
 //     staged weights are zero from the count on.  A zero weight contributes exactly zero for the same reason;
 //   * w1 / w2 are staged into LDS once per workgroup, one 64-float row per segment at a 68-float pitch (16-byte
 //     aligned float4 reads; the segments of a wave read disjoint banks);
-//   * the weighted sum is an fma chain in ascending rank inside the lane, then a butterfly over the group's lanes;
+//   * the weighted sum is an fp64 fma chain in ascending rank inside the lane, then a butterfly over the group's
+//     lanes, rounded to fp32 once;
 //   * pass 2 reads each column once: the power sums of the reliable rows shifted by c1, their min / max key (a
 //     constant column is ZERO_VARIANCE, decided exactly) and the sort keys come from the same registers; the
 //     cancellation guard re-reads a column whose mean sits far from c1;
@@ -46,7 +47,10 @@ constexpr int kPitch = 68;   // floats between the segments' weight rows in LDS
 
 // qtree / qtree_all, load_col and seg_sum below, and the pass-2 power sums with their cancellation guard in the
 // kernel, are copies of consensus_fast_f32.hip's (kept there untouched, so that kernel compiles as before): the two
-// must stay in step.  reduce_qr, rank_mask_general, round_verdict, stage_out / commit_staged are the shared headers.
+// must stay in step, with ONE difference, the guard's re-read.  There c1 is a median of the column and the re-read
+// stays in fp32 about c1 + dl; here the weights may put c1 anywhere, so the guard also fires on sums that are not
+// finite and the re-read works in fp64 about the fp64 mean of the reliable rows (see the guard in pass 2).
+// reduce_qr, rank_mask_general, round_verdict, stage_out / commit_staged are the shared headers.
 
 // Transposing butterfly over the wave's P columns (consensus_fast_f32.hip qtree_f): the lane ends with rows
 // I + base(lane) summed over all P columns.
@@ -93,9 +97,12 @@ SVOC_DEV void sort_col(uint32_t (&r)[64], int seg) {
 
 // sum_k w[k] x(k) over the group's sorted keys; w: this segment's 64 weights in LDS (16-byte aligned).  A term
 // enters only where its weight is non-zero: the sentinel keys (NaN) sit at ranks whose staged weight is zero.
+// Accumulated in fp64 and rounded to fp32 once: an fp32 chain rounds at the size of its partial sums, ~ w x the
+// largest |x|, and under weights that are not robust (outliers of both signs at weighted ranks) that is far more
+// than an ulp of the result -- enough to move the qr of the rows next to the centre past their tolerance.
 template <int NSEG, int P>
 SVOC_DEV float weighted_sum(const uint32_t (&r)[64], const float* w) {
-  float acc = 0.f;
+  double acc = 0.0;
 #pragma unroll
   for (int i = 0; i < 64; i += 4) {
     const float4 w4 = *(const float4*)(w + i);
@@ -103,10 +110,10 @@ SVOC_DEV float weighted_sum(const uint32_t (&r)[64], const float* w) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float x = fand(key_f32(r[i + j]), wv[j] != 0.f ? 0xffffffffu : 0u);
-      acc = __builtin_fmaf(wv[j], x, acc);
+      acc = __builtin_fma((double)wv[j], (double)x, acc);   // the product of two fp32 values is exact in fp64
     }
   }
-  return seg_sum<NSEG, P>(acc);
+  return (float)seg_sum<NSEG, P>(acc);
 }
 
 template <int NSEG, int WAVES, bool CONS>
@@ -271,28 +278,54 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(1)))
     double s3 = seg_sum<NSEG, P>((double)s3f), s4 = seg_sum<NSEG, P>((double)s4f);
     double shift = (double)c1c;
     // cancellation guard: when the reliable rows' mean sits far from c1 relative to their spread
-    // (mean offset^2 > 16 x variance), re-read the column once with the shift at the mean
+    // (mean offset^2 > 16 x variance), or the sums about c1 are not finite (s4 is the first to overflow, and it
+    // can only come out finite or +inf; the negated comparison is true for a NaN variance, but false for +inf),
+    // re-read the column once and take the moments as the CPU twin does: in fp64
+    // about the fp64 mean of the reliable rows.  The weights decide how far c1 follows the failing rows -- mean
+    // weights put it at (f / N) x the outliers -- so neither c1 + dl (dl carries the fp32 rounding of R terms ~ c1,
+    // which can exceed the reliable rows' spread) nor an fp32 power sum about it (2^80: y^2 overflows) will do.
     {
       const double dl = s1 * inv_n, mu2 = s2 * inv_n - dl * dl;
-      if (!constant && dl * dl > 16.0 * mu2) {
+      if (!constant && (!(dl * dl <= 16.0 * mu2) || !__builtin_isfinite(s4))) {
         uint64_t mm2 = mymask;
         asm volatile("" : "+v"(mm2));
-        const float sh2 = (float)((double)c1c + dl);
-        float t1 = 0.f, t2 = 0.f, t3 = 0.f, t4 = 0.f;
-        uint32_t xr[64];
-        load_col(rs, vo, rowb, xr);
+        // 16 rows at a time, the column read once for the mean and once for the moments: 64 raw values held
+        // across fp64 arithmetic would cost this (rare) branch more registers than the rest of the kernel needs
+        int rb2 = rowb;
+        asm volatile("" : "+s"(rb2));
+        double m = 0.0;
 #pragma unroll
-        for (int i = 0; i < 64; ++i) {
-          const float y = fand(__builtin_bit_cast(float, xr[i]) - sh2, bit_mask(mm2, i));
-          const float y2 = y * y;
-          t1 += y;
-          t2 += y2;
-          t3 = __builtin_fmaf(y2, y, t3);
-          t4 = __builtin_fmaf(y2, y2, t4);
+        for (int c = 0; c < 64; c += 16) {
+          uint32_t xr[16];
+#pragma unroll
+          for (int k = 0; k < 16; ++k) xr[k] = bload(rs, vo, (c + k) * rb2);
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int k = 0; k < 16; ++k) m += (double)fand(__builtin_bit_cast(float, xr[k]), bit_mask(mm2, c + k));
+          __builtin_amdgcn_sched_barrier(0);
         }
-        s1 = seg_sum<NSEG, P>((double)t1); s2 = seg_sum<NSEG, P>((double)t2);
-        s3 = seg_sum<NSEG, P>((double)t3); s4 = seg_sum<NSEG, P>((double)t4);
-        shift = (double)sh2;
+        m = seg_sum<NSEG, P>(m) * inv_n;
+        double t1 = 0.0, t2 = 0.0, t3 = 0.0, t4 = 0.0;
+#pragma unroll
+        for (int c = 0; c < 64; c += 16) {
+          uint32_t xr[16];
+#pragma unroll
+          for (int k = 0; k < 16; ++k) xr[k] = bload(rs, vo, (c + k) * rb2);
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int k = 0; k < 16; ++k) {
+            const double y = bit_mask(mm2, c + k) ? (double)__builtin_bit_cast(float, xr[k]) - m : 0.0;
+            const double y2 = y * y;
+            t1 += y;
+            t2 += y2;
+            t3 = __builtin_fma(y2, y, t3);
+            t4 = __builtin_fma(y2, y2, t4);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        s1 = seg_sum<NSEG, P>(t1); s2 = seg_sum<NSEG, P>(t2);
+        s3 = seg_sum<NSEG, P>(t3); s4 = seg_sum<NSEG, P>(t4);
+        shift = m;
       }
     }
     // central moments from the shifted sums
