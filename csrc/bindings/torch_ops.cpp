@@ -69,8 +69,9 @@ void fast_round_cpu(const at::Tensor& values, const c10::optional<at::Tensor>& a
                     const c10::optional<at::Tensor>& rst_saved, const c10::optional<at::Tensor>& rst_saved_en,
                     const c10::optional<at::Tensor>& rst_enabled, const c10::optional<at::Tensor>& rst_n_active,
                     const c10::optional<at::Tensor>& pend_rows, const c10::optional<at::Tensor>& pend_oracle,
-                    const c10::optional<at::Tensor>& pend_status) {
+                    const c10::optional<at::Tensor>& pend_status, const c10::optional<at::Tensor>& win_hint) {
   (void)wave_hint;
+  (void)win_hint;   // (GPU narrow-window hint; the CPU twin sorts whole columns)
   (void)work;
   (void)stats;   // (GPU pruned-network counter; the CPU twin runs full sorts)
   TORCH_CHECK(!upd_rows.has_value() || !upd_rows->defined(), "fused transactional streaming is a GPU path");
@@ -134,7 +135,7 @@ void fast_round_hip(const at::Tensor& values, const c10::optional<at::Tensor>& a
                     const c10::optional<at::Tensor>& rst_saved, const c10::optional<at::Tensor>& rst_saved_en,
                     const c10::optional<at::Tensor>& rst_enabled, const c10::optional<at::Tensor>& rst_n_active,
                     const c10::optional<at::Tensor>& pend_rows, const c10::optional<at::Tensor>& pend_oracle,
-                    const c10::optional<at::Tensor>& pend_status) {
+                    const c10::optional<at::Tensor>& pend_status, const c10::optional<at::Tensor>& win_hint) {
   fast_round_checks(values, D, c1, cons, skew, kurt, rel, qr, reliable, status);
   TORCH_CHECK(values.scalar_type() == at::kBFloat16 || values.scalar_type() == at::kFloat,
               "GPU fast path stores values in bf16 or fp32");
@@ -214,6 +215,17 @@ void fast_round_hip(const at::Tensor& values, const c10::optional<at::Tensor>& a
     TORCH_CHECK(stats->scalar_type() == at::kInt && stats->numel() >= 1 && stats->device() == values.device(),
                 "stats: int32 [>= 1] on the values' device ([0] += pruned-network fallbacks)");
     p.net_fallbacks = (unsigned int*)stats->data_ptr();
+    // [1] += narrow-window rounds, [2] += their columns recomputed for the window (FastParams.win_stats)
+    if (stats->numel() >= 3) p.win_stats = (unsigned int*)stats->data_ptr() + 1;
+  }
+  if (win_hint.has_value() && win_hint->defined()) {
+    TORCH_CHECK(win_hint->scalar_type() == at::kInt && win_hint->is_contiguous() && win_hint->numel() == B &&
+                    win_hint->device() == values.device(),
+                "win_hint: contiguous int32 [B] on the values' device");
+    // the fp32 window kernel's narrow stored window (FastParams.win_hint); every other round ignores the hint.
+    // SVOC_WIN_NARROW=0 (A/B): every round wide
+    const char* wn = std::getenv("SVOC_WIN_NARROW");
+    if (f32 && mode == 0 && !(wn && wn[0] == '0')) p.win_hint = win_hint->data_ptr<int32_t>();
   }
   for (const c10::optional<at::Tensor>* t : {&upd_rows, &upd_oracle, &upd_status, &rst_saved, &rst_saved_en,
                                               &rst_enabled, &rst_n_active})
@@ -561,7 +573,7 @@ TORCH_LIBRARY(svoc, m) {
       "Tensor? work=None, Tensor(i!)? stats=None, Tensor? upd_rows=None, Tensor? upd_oracle=None, "
       "Tensor(j!)? upd_status=None, int upd_per_inst=0, Tensor? rst_saved=None, Tensor? rst_saved_en=None, "
       "Tensor(k!)? rst_enabled=None, Tensor(l!)? rst_n_active=None, Tensor? pend_rows=None, "
-      "Tensor? pend_oracle=None, Tensor? pend_status=None) -> ()");
+      "Tensor? pend_oracle=None, Tensor? pend_status=None, Tensor(m!)? win_hint=None) -> ()");
   m.def(
       "exact_round(Tensor values, Tensor? active, int n_failing, bool constrained, int max_spread, "
       "Tensor(a!) c1, Tensor(b!) consensus, Tensor(c!) skew, Tensor(d!) kurt, Tensor(e!) rel, Tensor(f!) qr, "
@@ -578,6 +590,7 @@ TORCH_LIBRARY(svoc, m) {
   m.def("fast_work_words(int D) -> int", [](int64_t D) { return svoc::fast_work_words(D); });
   m.def("fast_win_h(int N, int n_failing) -> int",
         [](int64_t N, int64_t f) { return (int64_t)svoc::fast_win_h((int)N, (int)f); });
+  m.def("fast_win_narrow_hs() -> int", []() { return (int64_t)svoc::kWinfNarrowHs; });
   svoc::register_extra_defs(m);
 }
 

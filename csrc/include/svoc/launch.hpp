@@ -71,7 +71,20 @@ struct FastParams {
   uint8_t* rst_enabled;
   int32_t* rst_n_active;
   int rst_U;
+  // Narrow stored window (fp32 window kernel, N = 256, whole constrained rounds; null win_hint = off, every round
+  // wide): int32 [B] in device memory, 0 = this instance's round stores and reads the whole window, else only the
+  // kWinfNarrowHs keys on either side of the column median (the columns whose pass-2 pair falls outside are
+  // recomputed exactly).  Every round that reaches pass 2 writes the hint for the instance's next round: narrow
+  // when at most D / 64 of its columns would have fallen outside.  win_stats (null = not counted): [0] += narrow
+  // rounds, [1] += their columns recomputed for the window.  (Last in the struct: the fields above keep their
+  // kernel-argument offsets.)
+  int32_t* win_hint;
+  unsigned int* win_stats;
 };
+#ifndef SVOC_WINF_HS
+#define SVOC_WINF_HS 11
+#endif
+constexpr int kWinfNarrowHs = SVOC_WINF_HS;   // of H = 17; pass 2 then issues 32 + 2 * 11 + 5 = 59 loads per column
 
 // Workspace per instance of the LDS-free fast kernels, in u32 words (Dp = fast_work_pairs(D)).
 // bf16 kernels (column pairs):

@@ -176,7 +176,13 @@ SVOC_DEV bool try_pruned(uint32_t (&r)[64], int seg, int lane, uint32_t (&w)[WN]
 // network, window, c1 and qr pass run on the registers while it lands.  2 waves per SIMD (<= 256
 // VGPRs: 64 keys + 64 raw rows + the window), LDS = WAVES x 16 KiB.
 
-template <int NSEG, int WAVES, int H, bool CONS, int MODE, bool FUSED = false, bool DEFER = false, bool WIDE = false>
+// NARROW (FastParams.win_hint given; N = 256, whole constrained rounds): an instance whose hint is set runs a
+// narrow round -- pass 1 stores, and pass 2 reads, only the HS < H keys on either side of the column median
+// (window planes m = H - HS .. H - 1 of each part, at their usual workspace offsets).  Pass 2's pair lies in that
+// stored range unless many of the removed keys sit on one side of it (the trust predicate in pb_col); a column
+// that fails it gets the exact median in the cleanup, so a narrow round returns what a wide one does, bit for bit.
+template <int NSEG, int WAVES, int H, bool CONS, int MODE, bool FUSED = false, bool DEFER = false, bool WIDE = false,
+          bool NARROW = false>
 __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2))) void consensus_fast_winf_kernel(FastParams p) {
   // (no implicit fma contraction: the fused-streaming and plain instantiations compile their arithmetic in
   // different contexts and must still round alike -- tests/test_fast_transactional.py compares them bit for bit)
@@ -201,6 +207,13 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
   // deferred commit (FastParams.pend_rows): row -> its accepted update's slot in the pending batch (-1: none)
   __shared__ int spend[DEFER ? NPAD : 1];
   __shared__ uint32_t badu[8];
+  // narrow window: the columns whose pass-2 pair is not in the stored range (cleanup: exact median), their count
+  __shared__ uint32_t redow[NARROW ? 128 : 1];
+  __shared__ int win_fail[1];
+  static_assert(!NARROW || (NSEG == 4 && H == 17 && CONS && MODE == 0), "narrow window: N = 256, whole constrained rounds");
+  constexpr int HS = NARROW ? kWinfNarrowHs : H;   // stored half-width of a narrow round
+  constexpr int KN = H - HS;                       // its first stored plane
+  static_assert(HS >= 1 && (!NARROW || KN >= 1), "narrow window: 1 <= HS < H");
 
   const int b = blockIdx.x;
   static_assert(!FUSED || (MODE == 0 && CONS), "fused streaming: whole constrained rounds");
@@ -218,6 +231,13 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
   if (tid < 32) urow[tid] = 0;  // f < 32: unused slots still name a valid row
   if (tid == 0) misc_i[2] = 0;
   if (tid < 128) redo[tid] = 0u;
+  // (uniform; the LDS bit masks hold D <= 4096 columns: wider rounds stay wide)
+  bool nar = false;
+  if constexpr (NARROW) {
+    nar = __builtin_amdgcn_readfirstlane(p.win_hint[b]) != 0 && p.D <= 4096;
+    if (tid < 128) redow[tid] = 0u;
+    if (tid == 0) win_fail[0] = 0;
+  }
   const int seg = lane / P, cw = lane % P;
   const int N = p.N, D = p.D;
   const int rowb = p.ld * 4;
@@ -396,8 +416,9 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
   // One slab of phase A.  FULL: every column of the slab is < D and N = NPAD, so no masks at all; the
   // masked form serves the tail slab and padded N.  (One body per loop: reading the raw rows in two
   // branches of one loop makes the compiler demote them to scratch.)
-  auto slab_body = [&](auto full_c, int s) __attribute__((always_inline)) {
+  auto slab_body = [&](auto full_c, auto nar_c, int s) __attribute__((always_inline)) {
     constexpr bool FULL = decltype(full_c)::value;
+    constexpr int M0 = decltype(nar_c)::value ? KN : 0;   // first window plane stored
     const int col = s * W + wave * P + cw;
     const bool vc = FULL || col < D;
     int nvl = nv, nll = nl;
@@ -525,7 +546,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
           if (seg == slo || seg == slo + 1) {
             const int part = seg - slo;
 #pragma unroll
-            for (int m = 0; m < H; ++m) bstore(ws, wk[m], (part * Dc + col) * 4, 2 * m * Dc * 4);
+            for (int m = M0; m < H; ++m) bstore(ws, wk[m], (part * Dc + col) * 4, 2 * m * Dc * 4);
           }
         }
       } else {
@@ -561,10 +582,16 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
   };
   if constexpr (PASS1) {
     const int nfull = N == NPAD ? min(D / W, pass1_slabs) : 0;
+    // (a narrow round: its own loop -- the tail slab below stores every plane either way)
+    if (NARROW && nar) {
 #pragma nounroll
-    for (int s = 0; s < nfull; ++s) slab_body(std::true_type{}, s);
+      for (int s = 0; s < nfull; ++s) slab_body(std::true_type{}, std::integral_constant<bool, NARROW>{}, s);
+    } else {
 #pragma nounroll
-    for (int s = nfull; s < pass1_slabs; ++s) slab_body(std::false_type{}, s);
+      for (int s = 0; s < nfull; ++s) slab_body(std::true_type{}, std::false_type{}, s);
+    }
+#pragma nounroll
+    for (int s = nfull; s < pass1_slabs; ++s) slab_body(std::false_type{}, std::false_type{}, s);
   }
   if (!fused) break;
   __syncthreads();
@@ -655,6 +682,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
   if (CONS && !p.legacy) {
     const bool inwin = f + H <= N / 2;
     const int fr = first_reliable_row<4>(relmask);
+    const int zp = nar ? 2 * KN * Dc * 4 : 0;   // the outermost stored planes (the run covers them as well)
     bool zv = false;
 #pragma nounroll
     for (int base = wave * 64; base < D; base += WAVES * 64) {
@@ -663,7 +691,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
       bool cand = col < D;
       if (inwin) {
         // compared as values: a run of +0.0 and -0.0 is constant, but its keys differ
-        const uint32_t lo = bload(ws, pc * 4, 0), hi = ~bload(ws, (Dc + pc) * 4, 0);
+        const uint32_t lo = bload(ws, pc * 4, zp), hi = ~bload(ws, (Dc + pc) * 4, zp);
         cand = cand && fkey_val<true>(lo) == fkey_val<true>(hi);
       }
       if (__ballot(cand)) {   // rare: compare the reliable rows with the first one
@@ -709,7 +737,13 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
     uint32_t am[4];           // all-row power sums (phase A)
     float c1c;
   };
-  auto pb_load = [&](int base, PBWords& q) __attribute__((always_inline)) {
+  constexpr int NF = H == 17 ? 32 : 8;   // f at the sentinel-free shape (c3: N = 256, f = 32; N = 64, f = 8)
+  int win_failed = 0;                    // columns of this wave that failed the window's trust predicate (uniform)
+  // nar_c: a narrow round -- window planes KN .. H - 1 only, and on the sentinel-free path (uniform) only the f
+  // real removed rows, not the 2H network slots: 32 + 2 HS + 5 loads per column, within vmcnt's 63
+  auto pb_load = [&](auto nar_c, int base, PBWords& q) __attribute__((always_inline)) {
+    constexpr bool NAR = decltype(nar_c)::value;
+    constexpr int M0 = NAR ? KN : 0;
     const int col = base + lane;
     const int pc = col < D ? col : D - 1;
     const int vo = pc * 4;
@@ -719,16 +753,18 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
     const int s0 = CONS ? shl : 0;
     const uint64_t realm = ((fl >= 64 ? ~0ull : (1ull << fl) - 1)) << s0;
     q.c1c = p.c1[ob + pc];
+    const bool sfree = NAR && s0 == 0 && fl == NF;
 #pragma unroll
     for (int t = 0; t < NS; ++t) {
       const int row = t - s0;
       const bool real = (realm >> t) & 1;
       q.uw[t] = 0u;
-      if (CONS || real) q.uw[t] = row_load(__builtin_amdgcn_readfirstlane(urow[real ? row : 0]), vo);
+      if ((CONS || real) && !(NAR && t >= NF && sfree))
+        q.uw[t] = row_load(__builtin_amdgcn_readfirstlane(urow[real ? row : 0]), vo);
     }
     if constexpr (CONS) {
 #pragma unroll
-      for (int m = 0; m < H; ++m) {
+      for (int m = M0; m < H; ++m) {
         q.wl[m] = bload(ws, pc * 4, 2 * m * Dc * 4);
         q.wu[m] = ~bload(ws, (Dc + pc) * 4, 2 * m * Dc * 4);
       }
@@ -738,8 +774,10 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
   };
   float* const o_lds = reinterpret_cast<float*>(slab);   // [consensus | skew | kurt | c1] x D
   const bool ldso = CONS && PASS1 && D <= 4096;         // (4 D floats fit the WAVES x 16 KiB region)
-  auto pb_col = [&](auto ldso_c, int base, const PBWords& cur) __attribute__((always_inline)) {
+  auto pb_col = [&](auto ldso_c, auto nar_c, int base, const PBWords& cur) __attribute__((always_inline)) {
     constexpr bool LDSO = decltype(ldso_c)::value;
+    constexpr bool NAR = decltype(nar_c)::value;
+    constexpr int M0 = NAR ? KN : 0;
     const int col = base + lane;
     const float c1c = cur.c1c;
     int shl = sh, fl = f;
@@ -761,13 +799,14 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
       }
     }
     float cons_v = 0.f;
+    bool wtrust = true;
     if constexpr (CONS) {
       // lower window half: position c - H + m pairs with U'[m] (lo) / U'[m - 1] (hi); upper half
       // (stored complemented, position c + H - 1 - m): U'[2H - 1 - m] (lo) / U'[2H - 2 - m] (hi)
       auto cands = [&](const auto& z) __attribute__((always_inline)) {
         uint32_t clo = ~0u, chi = ~0u;
 #pragma unroll
-        for (int m = 0; m < H; ++m) {
+        for (int m = M0; m < H; ++m) {
           const uint32_t wl = cur.wl[m], wu = cur.wu[m];
           clo = kmin(clo, winf_cand(wl, z(m)));
           if (m) chi = kmin(chi, winf_cand(wl, z(m - 1)));
@@ -775,8 +814,23 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
           chi = kmin(chi, winf_cand(wu, z(2 * H - 2 - m)));
         }
         cons_v = 0.5f * (fkey_val<true>(clo) + fkey_val<true>(chi));
+        if constexpr (NARROW) {
+          // Trust predicate of the narrow window (stored indices j = KN .. T, T = 2H - 1 - KN; w[j] = wl[j] below
+          // H, wu[2H - 1 - j] above).  clo = w[j*], j* the first j with w[j] < U'[j]; chi = w[j**], j** the first
+          // j >= 1 with w[j] < U'[j - 1]; j* <= j**.
+          //   upper end: U'[T - 1] > w[T] (KN removed keys above the highest stored key) makes j = T a candidate
+          //     of chi, and so of clo: j* <= j** <= T.
+          //   lower end: U'[KN - 1] < w[KN] (KN removed keys below the lowest stored key).  j** < KN would need
+          //     w[j**] < U'[j** - 1] <= U'[KN - 1] < w[KN] with chi >= clo, and clo is not below w[KN]: w[KN] is
+          //     the key of full rank N/2 - H + KN, at least KN entries of U' (-inf sentinels counted: they stand
+          //     for the ranks pass 2's pair can not reach) are below it, so at most R/2 - 1 reliable keys are,
+          //     and the reliable key of rank R/2 - 1 (clo) is w[KN] or later; if j* < KN all the same, w[j*] =
+          //     w[KN] in value and KN is a candidate too (U'[KN] >= U'[j*] > w[j*]).
+          // Then the minima over j = KN .. T are the minima over every j.  Strict compares: on equality the
+          // column falls back.
+          wtrust = z(KN - 1) < cur.wl[KN] && z(2 * H - 2 - KN) > cur.wu[KN];
+        }
       };
-      constexpr int NF = H == 17 ? 32 : 8;   // f at the sentinel-free shape (c3: N = 256, f = 32; N = 64, f = 8)
       if (s0 == 0 && fl == NF) {   // (uniform) U' = the f sorted removed keys, then +inf: an NF-key network
         uint32_t z[NF];
 #pragma unroll
@@ -810,6 +864,9 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
       const double rdl = r1 * mk.in, rmu2 = r2 * mk.in - rdl * rdl;
       const double wc = (double)p.win_cancel;
       const bool good = r2 > 0.0 && a2 <= wc * r2 && a4 <= wc * r4 && rdl * rdl <= 4.0 * rmu2;
+      if constexpr (NAR) {
+        if (!wtrust) atomicOr(&redow[col >> 5], 1u << (col & 31));   // exact median below
+      }
       if constexpr (LDSO) {
         o_lds[col] = cons_v;
         o_lds[3 * D + col] = c1c;
@@ -841,39 +898,52 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
         bstore(ws, (uint32_t)col, k * 4, LST);
       }
     }
+    if constexpr (NARROW) win_failed += __popcll(__ballot(col < D && !wtrust));
   };
   if (ldso) {
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): no store in flight into the load-only loop
-    PBWords cur;
-    pb_load(wave * 64, cur);
+    auto pb_loop = [&](auto nar_c) __attribute__((always_inline)) {
+      PBWords cur;
+      pb_load(nar_c, wave * 64, cur);
 #pragma nounroll
-    for (int base = wave * 64; base < D; base += WAVES * 64) {
-      PBWords nxt;
-      if (base + WAVES * 64 < D) pb_load(base + WAVES * 64, nxt);   // uniform
-      // compiler barrier: the next column's loads are issued here, not sunk to their first use after the
-      // compute (the scheduler moves loads down to shorten live ranges)
-      asm volatile("" ::: "memory");
-      pb_col(std::true_type{}, base, cur);
-      cur = nxt;
-    }
+      for (int base = wave * 64; base < D; base += WAVES * 64) {
+        PBWords nxt;
+        if (base + WAVES * 64 < D) pb_load(nar_c, base + WAVES * 64, nxt);   // uniform
+        // compiler barrier: the next column's loads are issued here, not sunk to their first use after the
+        // compute (the scheduler moves loads down to shorten live ranges)
+        asm volatile("" ::: "memory");
+        pb_col(std::true_type{}, nar_c, base, cur);
+        cur = nxt;
+      }
+    };
+    if (NARROW && nar) pb_loop(std::integral_constant<bool, NARROW>{});
+    else pb_loop(std::false_type{});
   } else {
 #pragma nounroll
     for (int base = wave * 64; base < D; base += WAVES * 64) {
       PBWords cur;
-      pb_load(base, cur);
-      pb_col(std::false_type{}, base, cur);
+      pb_load(std::false_type{}, base, cur);
+      pb_col(std::false_type{}, std::false_type{}, base, cur);
     }
+  }
+  if constexpr (NARROW) {
+    if (lane == 0 && win_failed) atomicAdd(&win_fail[0], win_failed);
   }
   if (!CONS && zv && !p.legacy) misc_i[1] = 1;
   __syncthreads();
   // cleanup: one wave per listed column, lanes stride the rows, two-pass wave reductions
   // (math.cairo:320-363): the reliable mean first, then the power sums about it (no cancellation)
   // (ldso: the columns of the LDS bit mask in index order, dealt round-robin to the waves)
-  auto cleanup_col = [&](int col) __attribute__((always_inline)) {
+  // (narrow window -- mom / win, uniform: the column was listed for its moments' cancellation, for its window, or
+  // both; a window column also gets the exact smooth median of the reliable rows: every reliable key is ranked by
+  // counting, across the wave, the reliable keys below it (lt) and not above it (le); the key of sorted rank r is
+  // the one with lt <= r < le.  Same key <-> float mapping and the same 0.5f * (lo + hi) as pass 2.)
+  auto cleanup_col = [&](int col, bool mom, bool win) __attribute__((always_inline)) {
       const float cc = p.c1[ob + col];
       const float* xc = inst + col;
       float y[NSEG];
       float t1 = 0.f;
+      uint32_t ck[NSEG];   // the lane's reliable keys (narrow window)
 #pragma unroll
       for (int g = 0; g < NSEG; ++g) {
         const int i = g * 64 + lane;
@@ -887,6 +957,44 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
         }
         y[g] = use ? xv - cc : 0.f;
         t1 += y[g];
+        ck[g] = fkey<true>(f2u(xv));
+      }
+      if constexpr (NARROW) {
+        if (win) {
+          int lt[NSEG], le[NSEG];
+#pragma unroll
+          for (int g = 0; g < NSEG; ++g) lt[g] = le[g] = 0;
+#pragma unroll
+          for (int h = 0; h < NSEG; ++h) {
+            const uint64_t rm = relmask[h];   // uniform
+#pragma nounroll
+            for (int j = 0; j < 64; ++j) {
+              if (!((rm >> j) & 1)) continue;
+              const uint32_t kk = (uint32_t)__builtin_amdgcn_readlane((int)ck[h], j);
+#pragma unroll
+              for (int g = 0; g < NSEG; ++g) {
+                lt[g] += kk < ck[g];
+                le[g] += kk <= ck[g];
+              }
+            }
+          }
+          const int rl = R / 2 - 1, rh = R / 2;
+          uint32_t klo = 0u, khi = 0u;   // (every match holds the same key; no match: 0, below every key)
+#pragma unroll
+          for (int g = 0; g < NSEG; ++g) {
+            const bool use = g * 64 + lane < N && ((relmask[g] >> lane) & 1);
+            if (use && lt[g] <= rl && rl < le[g]) klo = ck[g];
+            if (use && lt[g] <= rh && rh < le[g]) khi = ck[g];
+          }
+          klo = kmax(klo, xor_lane_u32<1>(klo)); khi = kmax(khi, xor_lane_u32<1>(khi));
+          klo = kmax(klo, xor_lane_u32<2>(klo)); khi = kmax(khi, xor_lane_u32<2>(khi));
+          klo = kmax(klo, xor_lane_u32<4>(klo)); khi = kmax(khi, xor_lane_u32<4>(khi));
+          klo = kmax(klo, xor_lane_u32<8>(klo)); khi = kmax(khi, xor_lane_u32<8>(khi));
+          klo = kmax(klo, xor_lane_u32<16>(klo)); khi = kmax(khi, xor_lane_u32<16>(khi));
+          klo = kmax(klo, xor_lane_u32<32>(klo)); khi = kmax(khi, xor_lane_u32<32>(khi));
+          if (lane == 0) o_lds[col] = 0.5f * (fkey_val<true>(klo) + fkey_val<true>(khi));
+        }
+        if (!mom) return;
       }
       t1 += xor_lane<1>(t1); t1 += xor_lane<2>(t1); t1 += xor_lane<4>(t1);
       t1 += xor_lane<8>(t1); t1 += xor_lane<16>(t1); t1 += xor_lane<32>(t1);
@@ -930,11 +1038,14 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
   if (ldso) {
     int k = 0;
     for (int w32 = 0; w32 < (D + 31) / 32; ++w32) {
-      uint32_t bits = redo[w32];   // uniform
+      const uint32_t bm = redo[w32];   // uniform
+      uint32_t bw = 0u;
+      if constexpr (NARROW) bw = redow[w32];
+      uint32_t bits = bm | bw;
       while (bits) {
         const int c = __builtin_ctz(bits);
         bits &= bits - 1;
-        if (k % WAVES == wave) cleanup_col(w32 * 32 + c);
+        if (k % WAVES == wave) cleanup_col(w32 * 32 + c, (bm >> c) & 1, (bw >> c) & 1);
         ++k;
       }
     }
@@ -962,7 +1073,8 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
     if (nredo) {
       for (int k = wave; k < nredo; k += WAVES) {
         // (sc0: read through the vL1D -- the entry was written by another wave of this workgroup)
-        cleanup_col((int)__builtin_amdgcn_readfirstlane(__builtin_amdgcn_raw_buffer_load_b32(ws, 0, LST + k * 4, 1)));
+        cleanup_col((int)__builtin_amdgcn_readfirstlane(__builtin_amdgcn_raw_buffer_load_b32(ws, 0, LST + k * 4, 1)), true,
+                    false);
       }
       __syncthreads();
     }
@@ -987,32 +1099,54 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
     p.rel[2 * (int64_t)b] = misc_f[0];
     p.rel[2 * (int64_t)b + 1] = misc_f[1];
     p.status[b] = ST_OK;
+    if constexpr (NARROW) {
+      // the instance's next round: narrow while few columns need the exact median (a narrow round past the cap
+      // has just paid for them in the cleanup, once)
+      const int nf = win_fail[0];
+      p.win_hint[b] = nf <= D / 64 && D <= 4096 ? 1 : 0;
+      if (nar && p.win_stats) {
+        atomicAdd(p.win_stats, 1u);
+        if (nf) atomicAdd(p.win_stats + 1, (unsigned)nf);
+      }
+    }
   }
   upd_out(ST_OK);
+}
+
+// (hipLaunchKernelGGL is a macro: the instantiation's commas need a name)
+template <int NSEG, int WAVES, int H, bool CONS, int MODE, bool FUSED, bool DEFER, bool WIDE>
+static void launch_winf_k(const FastParams& p, hipStream_t stream) {
+  // the narrow-window form where the caller carries the instances' hints (N = 256, whole constrained rounds)
+  if constexpr (NSEG == 4 && H == 17 && CONS && MODE == 0) {
+    if (p.win_hint) {
+      auto k = consensus_fast_winf_kernel<NSEG, WAVES, H, CONS, MODE, FUSED, DEFER, WIDE, true>;
+      hipLaunchKernelGGL(k, dim3(p.B), dim3(WAVES * 64), 0, stream, p);
+      return;
+    }
+  }
+  auto k = consensus_fast_winf_kernel<NSEG, WAVES, H, CONS, MODE, FUSED, DEFER, WIDE>;
+  hipLaunchKernelGGL(k, dim3(p.B), dim3(WAVES * 64), 0, stream, p);
 }
 
 template <int NSEG, int WAVES, int H, bool CONS>
 static void launch_winf_w(const FastParams& p, hipStream_t stream) {
   if constexpr (CONS) {
     if (p.upd_rows && p.pend_rows) {   // ... with the previous batch's commit deferred into this round
-      hipLaunchKernelGGL((consensus_fast_winf_kernel<NSEG, WAVES, H, CONS, 0, true, true>), dim3(p.B),
-                         dim3(WAVES * 64), 0, stream, p);
+      launch_winf_k<NSEG, WAVES, H, CONS, 0, true, true, false>(p, stream);
       return;
     }
     if (p.upd_rows && p.upd_per_inst > 255) {   // ... with the 9-bit piece map
-      hipLaunchKernelGGL((consensus_fast_winf_kernel<NSEG, WAVES, H, CONS, 0, true, false, true>), dim3(p.B),
-                         dim3(WAVES * 64), 0, stream, p);
+      launch_winf_k<NSEG, WAVES, H, CONS, 0, true, false, true>(p, stream);
       return;
     }
     if (p.upd_rows) {   // fused transactional streaming (mode 0)
-      hipLaunchKernelGGL((consensus_fast_winf_kernel<NSEG, WAVES, H, CONS, 0, true>), dim3(p.B), dim3(WAVES * 64), 0,
-                         stream, p);
+      launch_winf_k<NSEG, WAVES, H, CONS, 0, true, false, false>(p, stream);
       return;
     }
   }
-  if (p.mode == 1) hipLaunchKernelGGL((consensus_fast_winf_kernel<NSEG, WAVES, H, CONS, 1>), dim3(p.B), dim3(WAVES * 64), 0, stream, p);
-  else if (p.mode == 2) hipLaunchKernelGGL((consensus_fast_winf_kernel<NSEG, WAVES, H, CONS, 2>), dim3(p.B), dim3(WAVES * 64), 0, stream, p);
-  else hipLaunchKernelGGL((consensus_fast_winf_kernel<NSEG, WAVES, H, CONS, 0>), dim3(p.B), dim3(WAVES * 64), 0, stream, p);
+  if (p.mode == 1) launch_winf_k<NSEG, WAVES, H, CONS, 1, false, false, false>(p, stream);
+  else if (p.mode == 2) launch_winf_k<NSEG, WAVES, H, CONS, 2, false, false, false>(p, stream);
+  else launch_winf_k<NSEG, WAVES, H, CONS, 0, false, false, false>(p, stream);
 }
 
 // 4-wave workgroups: 64 KiB of LDS slab each, two workgroups per CU (2 waves per SIMD) -- one's

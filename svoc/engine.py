@@ -201,8 +201,13 @@ class ConsensusEngine:
         # for the instances whose round reverts (engine docstring)
         self.transactional = mode == "fast"
         # pruned window network (fp32, N = 256): slab networks that failed the exact check and reran the
-        # full network, counted by the kernel (net_stats)
-        self._net_fb = torch.zeros(1, dtype=torch.int32, device=dev) if (mode == "fast" and dev.type == "cuda") else None
+        # full network, counted by the kernel (net_stats); [1], [2]: narrow-window rounds and their columns
+        # recomputed for the window
+        self._net_fb = torch.zeros(3, dtype=torch.int32, device=dev) if (mode == "fast" and dev.type == "cuda") else None
+        # narrow stored window of the fp32 window kernel (FastParams.win_hint): per instance, written by every
+        # round for the next one; zero = wide.  Device memory (graph capture replays it), not persisted.
+        self._win_hint = (torch.zeros(B, dtype=torch.int32, device=dev)
+                          if (mode == "fast" and dev.type == "cuda" and self.vdtype == torch.float32) else None)
         # exact rounds on the GPU: [rounds committed by the wide-column unconstrained kernel, rounds handed to the
         # i128 kernel] (consensus_wsadx.hip; exact_routing)
         self._xstats = torch.zeros(2, dtype=torch.int32, device=dev) if (mode == "exact" and dev.type == "cuda") else None
@@ -428,7 +433,8 @@ class ConsensusEngine:
                                      self.cfg.constrained, float(self.cfg.unconstrained_max_spread), v(self.c1),
                                      v(self.consensus), v(self.skew), v(self.kurt), v(self.rel), v(self.qr),
                                      v(self.reliable), v(self.status), self.wave_hint, 0, 0, self.cfg.legacy, w,
-                                     self._net_fb, **batch)
+                                     self._net_fb, win_hint=None if self._win_hint is None else v(self._win_hint),
+                                     **batch)
         else:
             self._ops.exact_round(v(self.values), active, self.cfg.n_failing_oracles, self.cfg.constrained,
                                   self.cfg.max_spread_wsad, v(self.c1), v(self.consensus), v(self.skew), v(self.kurt),
@@ -713,12 +719,16 @@ class ConsensusEngine:
     def net_stats(self) -> Dict[str, int]:
         """Pruned window network counters (fp32 storage, N = 256; sortnet.hpp window_group_pruned):
         ``slab_networks`` run so far (processed rounds x full 64-column slab steps x 4 waves) and the
-        ``fallbacks`` among them whose exact check failed (the full network reran for that wave)."""
+        ``fallbacks`` among them whose exact check failed (the full network reran for that wave).
+        ``narrow_rounds``: rounds that stored and read the narrow window (FastParams.win_hint), and
+        ``narrow_fallback_cols``: their columns that took the exact median instead."""
         self.pipeline_join()
         if self._net_fb is None or self._lest is not None or not self._route().pruned:
-            return {"slab_networks": 0, "fallbacks": 0}
+            return {"slab_networks": 0, "fallbacks": 0, "narrow_rounds": 0, "narrow_fallback_cols": 0}
         processed = int(self.metrics_fx[2].item())
-        return {"slab_networks": processed * (self.D // 64) * 4, "fallbacks": int(self._net_fb.item())}
+        fb = self._net_fb.tolist()
+        return {"slab_networks": processed * (self.D // 64) * 4, "fallbacks": int(fb[0]), "narrow_rounds": int(fb[1]),
+                "narrow_fallback_cols": int(fb[2])}
 
     def exact_routing(self) -> Dict[str, int]:
         """Exact engine on the GPU: how the rounds so far were computed -- ``processed`` rounds, of which
@@ -969,6 +979,8 @@ class ConsensusEngine:
         self.n_active.fill_(self.N)
         self.touched.fill_(1)
         self._all_active = True
+        if self._win_hint is not None:
+            self._win_hint.zero_()
 
     # ------------------------------------------------------------------ getters (contract ABI names)
     def get_consensus_value(self, i: Optional[int] = None) -> torch.Tensor:

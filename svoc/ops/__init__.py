@@ -126,3 +126,10 @@ def fast_work_numel(B: int, D: int) -> int:
 def fast_win_h(N: int, f: int) -> int:
     """Window half-width of the one-network kernels (launch.hpp fast_win_h): 5, 17, or 0 (no window)."""
     return ops().fast_win_h(N, f)
+
+
+def fast_win_narrow_hs() -> int:
+    """Stored half-width of a narrow round of the fp32 window kernel (launch.hpp kWinfNarrowHs, of H = 17):
+    ``fast_round(..., win_hint=<int32 [B]>)`` lets an instance whose hint is set store and read only that many keys
+    on either side of the column median; every round writes the hint for the instance's next round."""
+    return ops().fast_win_narrow_hs()
