@@ -71,7 +71,7 @@ struct FastParams {
   uint8_t* rst_enabled;
   int32_t* rst_n_active;
   int rst_U;
-  // Narrow stored window (fp32 window kernel, N = 256, whole constrained rounds; null win_hint = off, every round
+  // Narrow stored window (fp32 window kernel, 129 <= N <= 256 with H = 17, whole constrained rounds; null = off, every round
   // wide): int32 [B] in device memory, 0 = this instance's round stores and reads the whole window, else only the
   // kWinfNarrowHs keys on either side of the column median (the columns whose pass-2 pair falls outside are
   // recomputed exactly).  Every round that reaches pass 2 writes the hint for the instance's next round: narrow

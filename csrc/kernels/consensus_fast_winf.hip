@@ -176,7 +176,8 @@ SVOC_DEV bool try_pruned(uint32_t (&r)[64], int seg, int lane, uint32_t (&w)[WN]
 // network, window, c1 and qr pass run on the registers while it lands.  2 waves per SIMD (<= 256
 // VGPRs: 64 keys + 64 raw rows + the window), LDS = WAVES x 16 KiB.
 
-// NARROW (FastParams.win_hint given; N = 256, whole constrained rounds): an instance whose hint is set runs a
+// NARROW (FastParams.win_hint given; whole constrained fp32 rounds with four lane groups and H = 17, that is 129 <= N
+// <= 256 and roughly 9 <= f <= 32 -- not N = 256 alone; D <= 4096): an instance whose hint is set runs a
 // narrow round -- pass 1 stores, and pass 2 reads, only the HS < H keys on either side of the column median
 // (window planes m = H - HS .. H - 1 of each part, at their usual workspace offsets).  Pass 2's pair lies in that
 // stored range unless many of the removed keys sit on one side of it (the trust predicate in pb_col); a column
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
   // narrow window: the columns whose pass-2 pair is not in the stored range (cleanup: exact median), their count
   __shared__ uint32_t redow[NARROW ? 128 : 1];
   __shared__ int win_fail[1];
-  static_assert(!NARROW || (NSEG == 4 && H == 17 && CONS && MODE == 0), "narrow window: N = 256, whole constrained rounds");
+  static_assert(!NARROW || (NSEG == 4 && H == 17 && CONS && MODE == 0), "narrow window: 129 <= N <= 256 (four lane groups), H = 17, whole constrained rounds");
   constexpr int HS = NARROW ? kWinfNarrowHs : H;   // stored half-width of a narrow round
   constexpr int KN = H - HS;                       // its first stored plane
   static_assert(HS >= 1 && (!NARROW || KN >= 1), "narrow window: 1 <= HS < H");
@@ -1116,7 +1117,8 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
 // (hipLaunchKernelGGL is a macro: the instantiation's commas need a name)
 template <int NSEG, int WAVES, int H, bool CONS, int MODE, bool FUSED, bool DEFER, bool WIDE>
 static void launch_winf_k(const FastParams& p, hipStream_t stream) {
-  // the narrow-window form where the caller carries the instances' hints (N = 256, whole constrained rounds)
+  // the narrow-window form where the caller carries the instances' hints (129 <= N <= 256 with H = 17, whole
+  // constrained rounds; only N = 256, f = 32 takes pass 2's sentinel-free branch, the others pad U' with sentinels)
   if constexpr (NSEG == 4 && H == 17 && CONS && MODE == 0) {
     if (p.win_hint) {
       auto k = consensus_fast_winf_kernel<NSEG, WAVES, H, CONS, MODE, FUSED, DEFER, WIDE, true>;

@@ -721,14 +721,20 @@ class ConsensusEngine:
         ``slab_networks`` run so far (processed rounds x full 64-column slab steps x 4 waves) and the
         ``fallbacks`` among them whose exact check failed (the full network reran for that wave).
         ``narrow_rounds``: rounds that stored and read the narrow window (FastParams.win_hint), and
-        ``narrow_fallback_cols``: their columns that took the exact median instead."""
+        ``narrow_fallback_cols``: their columns that took the exact median instead -- counted wherever the
+        engine carries a hint (fp32 storage; a narrow round needs 129 <= N <= 256 and a window half-width of 17,
+        not the pruned network)."""
         self.pipeline_join()
-        if self._net_fb is None or self._lest is not None or not self._route().pruned:
-            return {"slab_networks": 0, "fallbacks": 0, "narrow_rounds": 0, "narrow_fallback_cols": 0}
-        processed = int(self.metrics_fx[2].item())
+        out = {"slab_networks": 0, "fallbacks": 0, "narrow_rounds": 0, "narrow_fallback_cols": 0}
+        if self._net_fb is None or self._lest is not None:
+            return out
         fb = self._net_fb.tolist()
-        return {"slab_networks": processed * (self.D // 64) * 4, "fallbacks": int(fb[0]), "narrow_rounds": int(fb[1]),
-                "narrow_fallback_cols": int(fb[2])}
+        if self._win_hint is not None:
+            out["narrow_rounds"], out["narrow_fallback_cols"] = int(fb[1]), int(fb[2])
+        if self._route().pruned:
+            processed = int(self.metrics_fx[2].item())
+            out["slab_networks"], out["fallbacks"] = processed * (self.D // 64) * 4, int(fb[0])
+        return out
 
     def exact_routing(self) -> Dict[str, int]:
         """Exact engine on the GPU: how the rounds so far were computed -- ``processed`` rounds, of which
